@@ -12,7 +12,13 @@ multiple execution contexts (reference examples/00_TensorRT/inference.cc
 pipeline). Weak scaling: per-GPU work is fixed as N grows.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+                       [--dump-outputs DIR] [--full]
   (for N>1 the driver launches via torch.distributed.run, one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the result
+line. --dump-outputs DIR additionally writes the output bindings of the
+last timed step as DIR/<binding>.npy (float32). --full adds the
+single-inflight request-latency phase (config.p50_ms / config.p99_ms).
 """
 from __future__ import annotations
 
@@ -71,6 +77,38 @@ class _TorchCommFallback:
         self._dist.destroy_process_group()
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # all dumped arrays together stay under 64 MB
+
+
+def _binding_as_float(view: np.ndarray, dtype: str) -> np.ndarray:
+    """Copy of an output binding as float32 (float64 for i32, exactly)."""
+    if dtype == "bf16":  # bindings carry bf16 bit patterns
+        bits = view.astype(np.uint16).astype(np.uint32) << 16
+        return bits.view(np.float32)
+    if dtype == "i32":
+        return view.astype(np.float64)
+    return view.astype(np.float32)
+
+
+def dump_outputs(ctx, out_dir: str) -> None:
+    """Write every output binding of `ctx` (as its caller would read them
+    after synchronize) to out_dir/<binding>.npy. A binding too large for
+    its share of the budget is reduced to a fixed seeded sample of its
+    flattened elements, identical from run to run."""
+    os.makedirs(out_dir, exist_ok=True)
+    bindings = ctx.plan.outputs
+    cap_bytes = DUMP_BUDGET_BYTES // max(len(bindings), 1)
+    for b in bindings:
+        arr = _binding_as_float(ctx.outputs[b["name"]], b["dtype"])
+        cap = cap_bytes // arr.dtype.itemsize
+        if arr.size > cap:
+            idx = np.sort(np.random.RandomState(0).randint(0, arr.size, cap))
+            arr = arr.reshape(-1)[idx]
+        fname = "".join(ch if ch.isalnum() or ch in "-_." else "_"
+                        for ch in b["name"])
+        np.save(os.path.join(out_dir, fname + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -85,7 +123,15 @@ def main():
                     choices=["fp16", "bf16", "int8", "fp8", "mxfp4", "mxfp8"])
     ap.add_argument("--no-autotune", action="store_true",
                     help="skip builder-time kernel tactic selection")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output bindings as "
+                         "DIR/<binding>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the single-inflight latency phase "
+                         "(p50_ms / p99_ms)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -227,23 +273,29 @@ def main():
         elapsed = comm.all_reduce_scalar(elapsed, op=OP_MAX)
         comm.barrier()
 
-    # ---- single-inflight latency phase (well-defined request latency:
-    # H2D + graph replay + D2H, one at a time; not part of the throughput
-    # measurement above) ----
+    # ---- outputs of the last timed step (all contexts are synchronized;
+    # the step ran on context (steps-1) % nc) ----
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctxs[(args.steps - 1) % nc], args.dump_outputs)
+
+    # ---- --full: single-inflight latency phase (well-defined request
+    # latency: H2D + graph replay + D2H, one at a time; not part of the
+    # throughput measurement above) ----
     lat1 = []
-    for _ in range(64):
-        t1 = time.perf_counter()
-        ctxs[0].launch()
-        ctxs[0].synchronize()
-        lat1.append((time.perf_counter() - t1) * 1e3)
-    if distributed:
-        comm.barrier()
+    if args.full:
+        for _ in range(64):
+            t1 = time.perf_counter()
+            ctxs[0].launch()
+            ctxs[0].synchronize()
+            lat1.append((time.perf_counter() - t1) * 1e3)
+        if distributed:
+            comm.barrier()
 
     if rank == 0:
         inf_s = n_gpus * args.steps * args.batch / elapsed
         ms_per_step = elapsed / args.steps * 1e3
-        p99 = float(np.percentile(lat1, 99))
-        p50 = float(np.percentile(lat1, 50))
+        p99 = float(np.percentile(lat1, 99)) if lat1 else None
+        p50 = float(np.percentile(lat1, 50)) if lat1 else None
         print(json.dumps({
             "metric": "inferences/sec",
             "value": round(inf_s, 2),
@@ -266,8 +318,11 @@ def main():
                 "parallelism": f"dp{n_gpus}",
                 "p50_ms": p50,
                 "p99_ms": p99,
-                "latency_note": "single-inflight request latency "
-                                "(H2D+forward+D2H, measured separately)",
+                "latency_note": ("single-inflight request latency "
+                                 "(H2D+forward+D2H, measured separately)"
+                                 if args.full else
+                                 "single-inflight latency not measured "
+                                 "(run with --full)"),
                 "pipelined_p99_ms": (float(np.percentile(lat_ms, 99))
                                      if lat_ms else None),
             },
