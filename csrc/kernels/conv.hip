@@ -118,8 +118,8 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(
   auto stage = [&](int t, int slot) {
     uint32_t base = lds0 + slot * kBuf;
     stage_conv_a<T, BM>(in, zero_page, p, m0, t * KT, base, tid);
-    stage_tile<T, BN>(Wt + (int64_t)n0 * p.K + (int64_t)t * KT, p.K, n0,
-                      p.Cout, base + kABytes, tid);
+    stage_tile<T, BN, true>(Wt + (int64_t)n0 * p.K + (int64_t)t * KT, p.K, n0,
+                            p.Cout, base + kABytes, tid);
   };
 
   if constexpr (NBUF == 4) {
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(
       __builtin_amdgcn_s_barrier();
       if (t + 3 < kt1) stage(t + 3, (t + 3 - kt0) & 3);
       const char* As = &smem[((t - kt0) & 3) * kBuf];
-      mfma_tile<T, BM, BN>(As, As + kABytes, lane, wr, wc, acc);
+      mfma_tile<T, BM, BN, true>(As, As + kABytes, lane, wr, wc, acc);
     }
   } else {
     stage(kt0, 0);
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(
     for (int t = kt0; t < kt1; ++t) {
       if (t + 1 < kt1) stage(t + 1, cur ^ 1);
       const char* As = &smem[cur * kBuf];
-      mfma_tile<T, BM, BN>(As, As + kABytes, lane, wr, wc, acc);
+      mfma_tile<T, BM, BN, true>(As, As + kABytes, lane, wr, wc, acc);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       cur ^= 1;
@@ -180,7 +180,8 @@ size_t conv_scratch_bytes(int Nb, int H, int W, int C, int Cout, int KH,
 // fragment row is one 128-B cacheline, B (the 64xK weight panel) stays
 // L2-resident across all M-tiles — and needs no LDS and no barrier.
 // MFMA A/B lane layout: lane holds 8 contiguous k at row lane&15,
-// k = (lane>>4)*8; D: col = lane&15, row = (lane>>4)*4 + r.
+// k = (lane>>4)*8; with the weight fragment first, D: row = lane&15,
+// channel = (lane>>4)*4 + r (gemm_common.h chan_of_frag_row).
 template <typename T, Epi E>
 __global__ __launch_bounds__(256) void conv_smallk_kernel(
     const T* __restrict__ A, const T* __restrict__ Bw, T* __restrict__ C,
@@ -196,9 +197,9 @@ __global__ __launch_bounds__(256) void conv_smallk_kernel(
   constexpr int kEps = MF::kStepBytes / (int)sizeof(T);    // 32 (fp16)
   constexpr int kFe = MF::kFragBytes / (int)sizeof(T);     // 8
   constexpr int kSteps = 128 / MF::kStepBytes;             // 2
-  f32x4 acc[4];
+  f32x4 acc[1][4];
 #pragma unroll
-  for (int f = 0; f < 4; ++f) acc[f] = {0.f, 0.f, 0.f, 0.f};
+  for (int f = 0; f < 4; ++f) acc[0][f] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int s = 0; s < kSteps; ++s) {
     int kb = s * kEps + (lane >> 4) * kFe;
@@ -206,33 +207,18 @@ __global__ __launch_bounds__(256) void conv_smallk_kernel(
         *(const typename MF::frag*)(A + (int64_t)arow * K + kb);
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
-      int brow = n0 + f * 16 + (lane & 15);
+      // channel-run mapping over the wave's 64 columns: weight first
+      int brow = n0 + (int)chan_of_frag_row<64>(f * 16 + (lane & 15));
       if (brow >= N) brow = N - 1;
       typename MF::frag bf =
           *(const typename MF::frag*)(Bw + (int64_t)brow * K + kb);
-      acc[f] = MF::run(af, bf, acc[f]);
+      acc[0][f] = MF::run(bf, af, acc[0][f]);
     }
   }
-#pragma unroll
-  for (int f = 0; f < 4; ++f) {
-    int col = n0 + f * 16 + (lane & 15);
-    if (col >= N) continue;
-    float sc = 1.0f, bi = 0.0f;
-    if constexpr (E == Epi::kScaleBias || E == Epi::kScaleBiasRelu ||
-                  E == Epi::kScaleBiasAddRelu || E == Epi::kScaleBiasGelu)
-      sc = scale[col];
-    if constexpr (E != Epi::kNone) bi = bias[col];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int row = m0 + wave * 16 + ((lane >> 4) << 2) + r;
-      if (row >= M) continue;
-      float res = 0.0f;
-      if constexpr (E == Epi::kScaleBiasAddRelu)
-        res = (float)residual[(int64_t)row * N + col] * res_scale;
-      C[(int64_t)row * N + col] =
-          store_cast<T>(apply_epi<E>(acc[f][r], sc, bi, res));
-    }
-  }
+  // lane: row wave*16 + (lane&15), 16 contiguous channels from (lane>>4)*16
+  store_chan_runs<E>(acc, C, (int64_t)N, m0 + wave * 16 + (lane & 15),
+                     n0 + (lane >> 4) * 16, M, N, scale, bias, residual,
+                     res_scale, 1.0f);
 }
 
 // ---- fused bottleneck tail: conv3x3+BN+ReLU -> conv1x1+BN+res+ReLU ----
@@ -292,7 +278,7 @@ __global__ __launch_bounds__(256) void bottleneck_tail_kernel(
       uint32_t base = lds0 + slot * kBuf;
       stage_conv_a<T, BM>(in, zero_page, p, m0, t * kTileElems<T>, base,
                           tid);
-      stage_tile<T, BNC>(W1 + (int64_t)nc * BNC * p.K +
+      stage_tile<T, BNC, true>(W1 + (int64_t)nc * BNC * p.K +
                              (int64_t)t * kTileElems<T>,
                          p.K, nc * BNC, CM, base + kABytes, tid);
     };
@@ -306,7 +292,7 @@ __global__ __launch_bounds__(256) void bottleneck_tail_kernel(
         __builtin_amdgcn_s_barrier();
         if (t + 3 < ktiles) stage1(t + 3, (t + 3) & 3);
         const char* As = &smem[(t & 3) * kBuf];
-        mfma_tile<T, BM, BNC>(As, As + kABytes, lane, wr, wc, acc1[nc]);
+        mfma_tile<T, BM, BNC, true>(As, As + kABytes, lane, wr, wc, acc1[nc]);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
@@ -318,7 +304,7 @@ __global__ __launch_bounds__(256) void bottleneck_tail_kernel(
       for (int t = 0; t < ktiles; ++t) {
         if (t + 1 < ktiles) stage1(t + 1, cur ^ 1);
         const char* As = &smem[cur * kBuf];
-        mfma_tile<T, BM, BNC>(As, As + kABytes, lane, wr, wc, acc1[nc]);
+        mfma_tile<T, BM, BNC, true>(As, As + kABytes, lane, wr, wc, acc1[nc]);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         cur ^= 1;
@@ -327,25 +313,34 @@ __global__ __launch_bounds__(256) void bottleneck_tail_kernel(
   }
 
   // ---- T -> LDS in swizzled A-tile layout (GEMM1 LDS slots are dead) ----
+  // Channel-run mapping: a lane holds 8 consecutive channels (= GEMM2 k
+  // elements) of one row, exactly one swizzled 16-byte chunk of the T tile.
+  static_assert(BNC == 64 && sizeof(T) == 2, "one 16-B chunk per lane");
 #pragma unroll
   for (int nc = 0; nc < NB1; ++nc) {
+    const int col0 = nc * BNC + wc * (BNC / 2) + (lane >> 4) * 8;
+    float sc[8], bi[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      sc[c] = s1[col0 + c];
+      bi[c] = b1[col0 + c];
+    }
 #pragma unroll
     for (int i = 0; i < BM / 32; ++i) {
+      uint32_t row = (uint32_t)(wr * (BM / 2) + i * 16 + (lane & 15));
+      __attribute__((aligned(16))) T o[8];
 #pragma unroll
-      for (int j = 0; j < BNC / 32; ++j) {
-        int col = nc * BNC + wc * (BNC / 2) + j * 16 + (lane & 15);
-        float sc = s1[col], bi = b1[col];
+      for (int j = 0; j < BNC / 32; ++j)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          uint32_t row =
-              (uint32_t)(wr * (BM / 2) + i * 16 + ((lane >> 4) << 2) + r);
-          float v = fmaxf((float)acc1[nc][i][j][r] * sc + bi, 0.0f);
-          uint32_t kb = (uint32_t)(col & 63) * (uint32_t)sizeof(T);
-          uint32_t off = (uint32_t)(col >> 6) * (uint32_t)kTBlk +
-                         (row << 7) + (kb ^ ((row & 7) << 4));
-          *(T*)(smem + off) = (T)v;
-        }
-      }
+        for (int r = 0; r < 4; ++r)
+          o[4 * j + r] = (T)fmaxf(
+              (float)acc1[nc][i][j][r] * sc[4 * j + r] + bi[4 * j + r], 0.0f);
+      uint32_t kb = (uint32_t)(col0 & 63) * (uint32_t)sizeof(T);
+      uint32_t off = (uint32_t)(col0 >> 6) * (uint32_t)kTBlk + (row << 7) +
+                     (kb ^ ((row & 7) << 4));
+      i32x4 t;
+      __builtin_memcpy(&t, o, 16);
+      *(i32x4*)(smem + off) = t;
     }
   }
   __syncthreads();
@@ -356,7 +351,7 @@ __global__ __launch_bounds__(256) void bottleneck_tail_kernel(
   for (int c2 = 0; c2 < Co / 64; ++c2) {
 #pragma unroll
     for (int t = 0; t < kT2; ++t)
-      stage_tile<T, 64>(W2 + (int64_t)c2 * 64 * CM + t * kTileElems<T>, CM,
+      stage_tile<T, 64, true>(W2 + (int64_t)c2 * 64 * CM + t * kTileElems<T>, CM,
                         c2 * 64, Co, (uint32_t)(uintptr_t)(B2s + t * 8192),
                         tid);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -368,7 +363,7 @@ __global__ __launch_bounds__(256) void bottleneck_tail_kernel(
       for (int j = 0; j < 2; ++j) acc2[i][j] = {0, 0, 0, 0};
 #pragma unroll
     for (int t = 0; t < kT2; ++t)
-      mfma_tile<T, BM, 64>(Tlds + t * kTBlk, B2s + t * 8192, lane, wr, wc,
+      mfma_tile<T, BM, 64, true>(Tlds + t * kTBlk, B2s + t * 8192, lane, wr, wc,
                            acc2);
     store_epilogue<T, Epi::kScaleBiasAddRelu, BM, 64>(
         acc2, out, Co, m0, c2 * 64, p.M, Co, s2, b2, residual, p.res_scale,

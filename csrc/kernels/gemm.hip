@@ -17,6 +17,10 @@
 //     stay adjacent (same XCD) per the split-K guidance.
 //   - split-K for K-heavy grid-starved shapes: fp32 slabs + a deterministic
 //     reduce kernel (splitk.hip) that applies the epilogue.
+//   - channel-run output mapping (gemm_common.h chan_of_frag_row): the
+//     weight fragment is the first MFMA operand and the B rows are staged
+//     interleaved, so a lane owns 8/16 contiguous output channels and the
+//     epilogue loads the residual and stores C 16 bytes at a time.
 //
 // Replaces the TensorRT-internal GEMM path of the reference
 // (trtlab/tensorrt/src/workspace.cc:47 enqueueV2 — opaque engine kernels).
@@ -74,8 +78,8 @@ __global__ __launch_bounds__(256) void gemm_bt_kernel(
     uint32_t base = lds0 + slot * kBuf;
     stage_tile<T, BM>(A + (int64_t)m0 * lda + (int64_t)t * KT, lda, m0, M,
                       base, tid);
-    stage_tile<T, BN>(B + (int64_t)n0 * ldb + (int64_t)t * KT, ldb, n0, N,
-                      base + kABytes, tid);
+    stage_tile<T, BN, true>(B + (int64_t)n0 * ldb + (int64_t)t * KT, ldb, n0,
+                            N, base + kABytes, tid);
   };
 
   if constexpr (NBUF == 4) {
@@ -90,7 +94,7 @@ __global__ __launch_bounds__(256) void gemm_bt_kernel(
       __builtin_amdgcn_s_barrier();
       if (t + 3 < kt1) stage(t + 3, (t + 3 - kt0) & 3);
       const char* As = &smem[((t - kt0) & 3) * kBuf];
-      mfma_tile<T, BM, BN>(As, As + kABytes, lane, wr, wc, acc);
+      mfma_tile<T, BM, BN, true>(As, As + kABytes, lane, wr, wc, acc);
     }
   } else if constexpr (NBUF == 3) {
     // 2-deep counted pipeline (the 256-wide tile: 4 slots would overflow
@@ -105,7 +109,7 @@ __global__ __launch_bounds__(256) void gemm_bt_kernel(
       __builtin_amdgcn_s_barrier();
       if (t + 2 < kt1) stage(t + 2, (t + 2 - kt0) % 3);
       const char* As = &smem[((t - kt0) % 3) * kBuf];
-      mfma_tile<T, BM, BN>(As, As + kABytes, lane, wr, wc, acc);
+      mfma_tile<T, BM, BN, true>(As, As + kABytes, lane, wr, wc, acc);
     }
   } else {
     stage(kt0, 0);
@@ -115,7 +119,7 @@ __global__ __launch_bounds__(256) void gemm_bt_kernel(
     for (int t = kt0; t < kt1; ++t) {
       if (t + 1 < kt1) stage(t + 1, cur ^ 1);
       const char* As = &smem[cur * kBuf];
-      mfma_tile<T, BM, BN>(As, As + kABytes, lane, wr, wc, acc);
+      mfma_tile<T, BM, BN, true>(As, As + kABytes, lane, wr, wc, acc);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       cur ^= 1;

@@ -128,9 +128,29 @@ __device__ __forceinline__ void glds16(const void* gsrc, uint32_t lds_byte) {
       0);
 }
 
+// Channel-run output mapping. With the weight fragment as the FIRST MFMA
+// operand, D arrives as row m = lane&15, channel = 4*(lane>>4) + r: four
+// consecutive channels per lane. Which weight row sits behind which MFMA
+// input lane is free to choose, so the NF = COLS/16 fragments of a wave's
+// COLS-channel span are interleaved: fragment j, input lane q carries
+// channel (q>>2)*(4*NF) + 4*j + (q&3). A lane then owns 4*NF CONTIGUOUS
+// channels of one output row (8 for a 32-wide span, 16 for a 64-wide one)
+// and the epilogue moves 16 bytes per instruction. The permutation is
+// applied where the weight rows are fetched from global memory, so the LDS
+// image keeps its fragment-major rows and the conflict-free swizzled reads;
+// the k order of every dot product is unchanged.
+template <int COLS>
+__device__ __forceinline__ uint32_t chan_of_frag_row(uint32_t r) {
+  constexpr uint32_t NF = COLS / 16;
+  uint32_t j = r >> 4, q = r & 15;
+  return (q >> 2) * (4 * NF) + 4 * j + (q & 3);
+}
+
 // Stage a ROWS x 64-elem tile of a row-major matrix into LDS, rows clamped
-// to [0, nrows). Source-side XOR swizzle (rule 21). ROWS in {64, 128}.
-template <typename T, int ROWS>
+// to [0, nrows). Source-side XOR swizzle (rule 21). ROWS in {64, 128, 256}.
+// CHAN_RUNS: the tile is a weight (B) tile for the channel-run mapping —
+// LDS row r of each wave half (ROWS/2 rows) holds chan_of_frag_row(r).
+template <typename T, int ROWS, bool CHAN_RUNS = false>
 __device__ __forceinline__ void stage_tile(const T* __restrict__ src,
                                            int64_t stride_elems, int row0,
                                            int nrows, uint32_t lds_base,
@@ -140,7 +160,12 @@ __device__ __forceinline__ void stage_tile(const T* __restrict__ src,
     uint32_t p = c * 4096 + tid * 16;
     uint32_t row = p >> 7;
     uint32_t kb = (p & 127) ^ ((row & 7) << 4);
-    int r = row0 + (int)row;
+    uint32_t srow = row;
+    if constexpr (CHAN_RUNS) {
+      constexpr uint32_t kHalf = ROWS / 2;
+      srow = (row & ~(kHalf - 1)) + chan_of_frag_row<kHalf>(row & (kHalf - 1));
+    }
+    int r = row0 + (int)srow;
     r = (r < 0) ? 0 : (r >= nrows ? nrows - 1 : r);
     const char* g = (const char*)src +
                     ((int64_t)r - row0) * stride_elems * (int64_t)sizeof(T) +
@@ -162,7 +187,11 @@ __device__ __forceinline__ typename Mfma16x16x32<T>::frag read_frag(
 // ---------------------------------------------------------- tiled compute
 // Shared MFMA core for gemm/conv: 4 waves as 2x2, wave tile (BM/2)x(BN/2),
 // fragments of 16x16x32, BK=64 (two MFMA k-steps per staged tile).
-template <typename T, int BM, int BN>
+// CHAN_RUNS = false: activation fragment first, D is col = lane&15,
+// row = 4*(lane>>4) + r (four consecutive ROWS per lane).
+// CHAN_RUNS = true: weight fragment first (B staged with CHAN_RUNS), D is
+// row = lane&15, four consecutive CHANNELS per lane — see chan_of_frag_row.
+template <typename T, int BM, int BN, bool CHAN_RUNS = false>
 __device__ __forceinline__ void mfma_tile(
     const char* As, const char* Bs, int lane, int wr, int wc,
     typename Mfma16x16x32<T>::accv (&acc)[BM / 32][BN / 32]) {
@@ -182,14 +211,137 @@ __device__ __forceinline__ void mfma_tile(
 #pragma unroll
     for (int i = 0; i < MFr; ++i)
 #pragma unroll
-      for (int j = 0; j < NFr; ++j)
-        acc[i][j] = MF::run(af[i], bf[j], acc[i][j]);
+      for (int j = 0; j < NFr; ++j) {
+        if constexpr (CHAN_RUNS)
+          acc[i][j] = MF::run(bf[j], af[i], acc[i][j]);
+        else
+          acc[i][j] = MF::run(af[i], bf[j], acc[i][j]);
+      }
   }
 }
 
-// Shared predicated epilogue store. D mapping for 16x16x32 MFMA:
-// col = lane&15, row = (lane>>4)*4 + r. OT = output/residual element type
-// (defaults to the compute type; fp8-in/fp16-out gemms set OT=_Float16).
+// Raw 4/8/16-byte register image of a packed run of output elements.
+template <int BYTES>
+struct RawVec;
+template <>
+struct RawVec<4> { using type = int; };
+template <>
+struct RawVec<8> { using type = i32x2; };
+template <>
+struct RawVec<16> { using type = i32x4; };
+
+template <Epi E>
+constexpr bool kEpiHasScale =
+    E == Epi::kScaleBias || E == Epi::kScaleBiasRelu ||
+    E == Epi::kScaleBiasAddRelu || E == Epi::kScaleBiasGelu;
+
+// Epilogue store for accumulators in the channel-run mapping: this lane
+// holds output rows row0 + 16*i (i < MF) and the 4*NF contiguous channels
+// col0 + 4*j + r of each. The run is moved in vectors of up to 16 bytes
+// (fp16/bf16: 8 channels per store; 1-byte formats: the whole run): scale
+// and bias as float4 groups, the residual with one load per vector.
+// A lane takes the vector path only if its whole run lies inside N and
+// C, the row pitch and the residual are aligned to the vector (scale/bias
+// to 16 B); otherwise it falls back to scalar column-predicated accesses
+// (N=1000 classifier heads, odd ldc, offset sub-matrix views). Rows are
+// predicated against M on both paths. OT = output/residual element type.
+template <Epi E, typename AccV, int MF, int NF, typename OT>
+__device__ __forceinline__ void store_chan_runs(
+    AccV (&acc)[MF][NF], OT* __restrict__ C, int64_t ldc, int row0, int col0,
+    int M, int N, const float* __restrict__ scale,
+    const float* __restrict__ bias, const OT* __restrict__ residual,
+    float res_scale, float out_scale) {
+  constexpr bool kRes = E == Epi::kScaleBiasAddRelu;
+  constexpr int CH = 4 * NF;  // channels per lane
+  constexpr int VE = (16 / (int)sizeof(OT) < CH) ? 16 / (int)sizeof(OT) : CH;
+  constexpr int VB = VE * (int)sizeof(OT);  // bytes per vector access
+  constexpr int JV = VE / 4;                // fragments per vector
+  using RV = typename RawVec<VB>::type;
+
+  uintptr_t mis = (uintptr_t)C | (uintptr_t)(ldc * (int64_t)sizeof(OT));
+  if constexpr (kRes) mis |= (uintptr_t)residual;
+  uintptr_t mis16 = 0;
+  if constexpr (kEpiHasScale<E>) mis16 |= (uintptr_t)scale;
+  if constexpr (E != Epi::kNone) mis16 |= (uintptr_t)bias;
+  const bool vec =
+      col0 + CH <= N && (mis & (VB - 1)) == 0 && (mis16 & 15) == 0;
+
+  if (vec) {
+#pragma unroll
+    for (int v = 0; v < CH / VE; ++v) {
+      const int colv = col0 + v * VE;
+      f32x4 sc[JV], bi[JV];
+#pragma unroll
+      for (int jj = 0; jj < JV; ++jj) {
+        sc[jj] = {1.0f, 1.0f, 1.0f, 1.0f};
+        bi[jj] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (kEpiHasScale<E>)
+          sc[jj] = *(const f32x4*)(scale + colv + 4 * jj);
+        if constexpr (E != Epi::kNone)
+          bi[jj] = *(const f32x4*)(bias + colv + 4 * jj);
+      }
+#pragma unroll
+      for (int i = 0; i < MF; ++i) {
+        int row = row0 + i * 16;
+        if (row >= M) continue;
+        int64_t off = (int64_t)row * ldc + colv;
+        __attribute__((aligned(16))) OT rs[VE];
+        __attribute__((aligned(16))) OT o[VE];
+        if constexpr (kRes) {
+          RV t = *(const RV*)(residual + off);
+          __builtin_memcpy(rs, &t, VB);
+        }
+#pragma unroll
+        for (int jj = 0; jj < JV; ++jj)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            float res = 0.0f;
+            if constexpr (kRes) res = (float)rs[4 * jj + r] * res_scale;
+            float val = apply_epi<E>((float)acc[i][v * JV + jj][r], sc[jj][r],
+                                     bi[jj][r], res);
+            o[4 * jj + r] = store_cast<OT>(val * out_scale);
+            // scale+bias with nothing after it: keep each conversion a
+            // scalar so it fuses with the fma into v_fma_mixlo_f16 (one
+            // rounding, fma -> fp16) exactly as on the scalar fallback
+            // path; packed, it would round to fp32 first and differ by
+            // one fp16 ulp in ~6e-5 of the elements, by alignment.
+            if constexpr (E == Epi::kScaleBias &&
+                          std::is_same<OT, _Float16>::value)
+              asm("" : "+v"(o[4 * jj + r]));
+          }
+        RV t;
+        __builtin_memcpy(&t, o, VB);
+        *(RV*)(C + off) = t;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        int col = col0 + 4 * j + r;
+        if (col >= N) continue;
+        float sc = 1.0f, bi = 0.0f;
+        if constexpr (kEpiHasScale<E>) sc = scale[col];
+        if constexpr (E != Epi::kNone) bi = bias[col];
+#pragma unroll
+        for (int i = 0; i < MF; ++i) {
+          int row = row0 + i * 16;
+          if (row >= M) continue;
+          float res = 0.0f;
+          if constexpr (kRes)
+            res = (float)residual[(int64_t)row * ldc + col] * res_scale;
+          float val = apply_epi<E>((float)acc[i][j][r], sc, bi, res);
+          C[(int64_t)row * ldc + col] = store_cast<OT>(val * out_scale);
+        }
+      }
+    }
+  }
+}
+
+// Shared predicated epilogue store for the 2x2-wave tile computed by
+// mfma_tile<..., CHAN_RUNS = true>: row = lane&15 within each row
+// fragment, channels (lane>>4)*4*NFr .. +4*NFr-1 of the wave's column half.
 template <typename T, Epi E, int BM, int BN, typename OT = T>
 __device__ __forceinline__ void store_epilogue(
     typename Mfma16x16x32<T>::accv (&acc)[BM / 32][BN / 32],
@@ -197,30 +349,10 @@ __device__ __forceinline__ void store_epilogue(
     const float* __restrict__ scale, const float* __restrict__ bias,
     const OT* __restrict__ residual, float res_scale, int lane, int wr,
     int wc, float out_scale = 1.0f) {
-  constexpr int MFr = BM / 32, NFr = BN / 32;
-#pragma unroll
-  for (int i = 0; i < MFr; ++i) {
-#pragma unroll
-    for (int j = 0; j < NFr; ++j) {
-      int col = n0 + wc * (BN / 2) + j * 16 + (lane & 15);
-      if (col >= N) continue;
-      float sc = 1.0f, bi = 0.0f;
-      if constexpr (E == Epi::kScaleBias || E == Epi::kScaleBiasRelu ||
-                    E == Epi::kScaleBiasAddRelu || E == Epi::kScaleBiasGelu)
-        sc = scale[col];
-      if constexpr (E != Epi::kNone) bi = bias[col];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int row = m0 + wr * (BM / 2) + i * 16 + ((lane >> 4) << 2) + r;
-        if (row >= M) continue;
-        float res = 0.0f;
-        if constexpr (E == Epi::kScaleBiasAddRelu)
-          res = (float)residual[(int64_t)row * ldc + col] * res_scale;
-        float v = apply_epi<E>((float)acc[i][j][r], sc, bi, res);
-        C[(int64_t)row * ldc + col] = store_cast<OT>(v * out_scale);
-      }
-    }
-  }
+  int row0 = m0 + wr * (BM / 2) + (lane & 15);
+  int col0 = n0 + wc * (BN / 2) + (lane >> 4) * (BN / 8);
+  store_chan_runs<E>(acc, C, ldc, row0, col0, M, N, scale, bias, residual,
+                     res_scale, out_scale);
 }
 
 // ------------------------------------------------- deep staging pipeline
@@ -282,22 +414,24 @@ inline bool want_deep_pipe(long blocks, int ktiles) {
   return blocks < gate && ktiles >= 2;
 }
 
-// Split-K slab store: this (tile, slice)'s [BM][BN] fp32 partial sums.
+// Split-K slab store: this (tile, slice)'s [BM][BN] row-major fp32 partial
+// sums, from the channel-run mapping — one float4 per (row, fragment); the
+// slab base is 16-byte aligned (BM*BN*4-byte slabs in an aligned scratch).
 template <typename T, int BM, int BN>
 __device__ __forceinline__ void store_splitk(
     typename Mfma16x16x32<T>::accv (&acc)[BM / 32][BN / 32],
     float* __restrict__ slab, int lane, int wr, int wc) {
+  const int col0 = wc * (BN / 2) + (lane >> 4) * (BN / 8);
 #pragma unroll
-  for (int i = 0; i < BM / 32; ++i)
+  for (int i = 0; i < BM / 32; ++i) {
+    int row = wr * (BM / 2) + i * 16 + (lane & 15);
 #pragma unroll
     for (int j = 0; j < BN / 32; ++j) {
-      int col = wc * (BN / 2) + j * 16 + (lane & 15);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int row = wr * (BM / 2) + i * 16 + ((lane >> 4) << 2) + r;
-        slab[row * BN + col] = (float)acc[i][j][r];
-      }
+      f32x4 v = {(float)acc[i][j][0], (float)acc[i][j][1],
+                 (float)acc[i][j][2], (float)acc[i][j][3]};
+      *(f32x4*)(slab + row * BN + col0 + 4 * j) = v;
     }
+  }
 }
 
 // Split-K decision: only for severely grid-starved, K-heavy shapes (the

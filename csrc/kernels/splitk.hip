@@ -5,7 +5,9 @@
 // slice writes an fp32 [BM][BN] slab, and this kernel sums the slices and
 // applies the fused epilogue. Deterministic (no atomics). Vectorized
 // float4 slab reads, grid-strided over the whole slab set; bm*bn is a
-// power of two so tile/element decomposition is shifts.
+// power of two so tile/element decomposition is shifts. Each thread's 4
+// consecutive columns leave as one packed store (8 B fp16/bf16), with the
+// residual read the same way, through the shared channel-run epilogue.
 #include "gemm_common.h"
 
 namespace trtlab {
@@ -38,21 +40,11 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ scratch,
     int row = m0 + e / bn;
     int col0 = n0 + e % bn;  // 4 consecutive cols (bn % 4 == 0)
     if (row >= M) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      int col = col0 + j;
-      if (col >= N) continue;
-      float sc = 1.0f, bi = 0.0f;
-      if constexpr (E == Epi::kScaleBias || E == Epi::kScaleBiasRelu ||
-                    E == Epi::kScaleBiasAddRelu || E == Epi::kScaleBiasGelu)
-        sc = scale[col];
-      if constexpr (E != Epi::kNone) bi = bias[col];
-      float res = 0.0f;
-      if constexpr (E == Epi::kScaleBiasAddRelu)
-        res = (float)residual[(int64_t)row * ldc + col] * res_scale;
-      float vv = j == 0 ? v.x : (j == 1 ? v.y : (j == 2 ? v.z : v.w));
-      C[(int64_t)row * ldc + col] = store_cast<T>(apply_epi<E>(vv, sc, bi, res));
-    }
+    // the 4 columns are one fragment of a channel run starting at col0:
+    // packed 4-element store / residual load when aligned, scalar otherwise
+    f32x4 acc[1][1] = {{{v.x, v.y, v.z, v.w}}};
+    store_chan_runs<E>(acc, C, ldc, row, col0, M, N, scale, bias, residual,
+                       res_scale, 1.0f);
   }
 }
 
