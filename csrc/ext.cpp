@@ -654,121 +654,46 @@ PYBIND11_MODULE(_C, m) {
           py::arg("C"), py::arg("M"), py::arg("N"), py::arg("K"),
           py::arg("stream") = 0, py::arg("sync") = true);
   ops.def("kv_append",
-          [](uintptr_t qkv, uintptr_t kc, uintptr_t vc, uintptr_t pos, int B,
-             int H, int smax, uintptr_t stream, bool sync, int D) {
-            launch_kv_append((void*)qkv, (void*)kc, (void*)vc, (void*)pos, B,
-                             H, smax, as_stream(stream), D);
-            if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
-          },
-          py::arg("qkv"), py::arg("kcache"), py::arg("vcache"),
-          py::arg("pos"), py::arg("B"), py::arg("H"), py::arg("smax"),
-          py::arg("stream") = 0, py::arg("sync") = true,
-          py::arg("D") = 64);
-  ops.def("kv_append_range",
-          [](uintptr_t qkv, uintptr_t kc, uintptr_t vc, int B, int H, int P,
-             int smax, uintptr_t stream, bool sync, int D) {
-            launch_kv_append_range((void*)qkv, (void*)kc, (void*)vc, B, H, P,
-                                   smax, as_stream(stream), D);
+          [](uintptr_t qkv, uintptr_t kc, uintptr_t vc, int B, int H,
+             int rows, int smax, uintptr_t pos, uintptr_t table,
+             int max_pages, uintptr_t stream, bool sync, int D) {
+            launch_kv_append((void*)qkv, (void*)kc, (void*)vc, (void*)pos,
+                             (void*)table, max_pages, B, H, rows, smax,
+                             as_stream(stream), D);
             if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
           },
           py::arg("qkv"), py::arg("kcache"), py::arg("vcache"), py::arg("B"),
-          py::arg("H"), py::arg("P"), py::arg("smax"), py::arg("stream") = 0,
-          py::arg("sync") = true, py::arg("D") = 64);
-  ops.def("kv_append_chunk_paged",
-          [](uintptr_t qkv, uintptr_t kpool, uintptr_t vpool,
-             uintptr_t table, uintptr_t pos, int B, int H, int K,
-             int max_pages, uintptr_t stream, bool sync, int D) {
-            launch_kv_append_chunk_paged((void*)qkv, (void*)kpool,
-                                         (void*)vpool, (void*)table,
-                                         (void*)pos, B, H, K, max_pages,
-                                         as_stream(stream), D);
-            if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
-          },
-          py::arg("qkv"), py::arg("kpool"), py::arg("vpool"),
-          py::arg("table"), py::arg("pos"), py::arg("B"), py::arg("H"),
-          py::arg("K"), py::arg("max_pages"), py::arg("stream") = 0,
-          py::arg("sync") = true, py::arg("D") = 64);
-  ops.def("kv_append_range_paged",
-          [](uintptr_t qkv, uintptr_t kpool, uintptr_t vpool,
-             uintptr_t table, int B, int H, int P, int max_pages,
-             uintptr_t stream, bool sync, int D) {
-            launch_kv_append_range_paged((void*)qkv, (void*)kpool,
-                                         (void*)vpool, (void*)table, B, H,
-                                         P, max_pages, as_stream(stream),
-                                         D);
-            if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
-          },
-          py::arg("qkv"), py::arg("kpool"), py::arg("vpool"),
-          py::arg("table"), py::arg("B"), py::arg("H"), py::arg("P"),
-          py::arg("max_pages"), py::arg("stream") = 0,
-          py::arg("sync") = true, py::arg("D") = 64);
-  ops.def("chunk_attention_paged",
-          [](uintptr_t qkv, uintptr_t kpool, uintptr_t vpool, uintptr_t out,
-             uintptr_t table, uintptr_t pos, int B, int H, int K,
-             int max_pages, float scale, uintptr_t stream, bool sync,
-             int D) {
-            launch_chunk_attention_paged((void*)qkv, (void*)kpool,
-                                         (void*)vpool, (void*)out,
-                                         (void*)table, (void*)pos, B, H, K,
-                                         max_pages, scale,
-                                         as_stream(stream), D);
-            if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
-          },
-          py::arg("qkv"), py::arg("kpool"), py::arg("vpool"),
-          py::arg("out"), py::arg("table"), py::arg("pos"), py::arg("B"),
-          py::arg("H"), py::arg("K"), py::arg("max_pages"),
-          py::arg("scale"), py::arg("stream") = 0, py::arg("sync") = true,
-          py::arg("D") = 64);
-  ops.def("kv_append_paged",
-          [](uintptr_t qkv, uintptr_t kp, uintptr_t vp, uintptr_t table,
-             uintptr_t pos, int B, int H, int max_pages, uintptr_t stream,
-             bool sync, int D) {
-            launch_kv_append_paged((void*)qkv, (void*)kp, (void*)vp,
-                                   (void*)table, (void*)pos, B, H,
-                                   max_pages, as_stream(stream), D);
-            if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
-          },
-          py::arg("qkv"), py::arg("kpool"), py::arg("vpool"),
-          py::arg("table"), py::arg("pos"), py::arg("B"), py::arg("H"),
-          py::arg("max_pages"), py::arg("stream") = 0,
-          py::arg("sync") = true, py::arg("D") = 64);
-  ops.def("decode_attention_paged",
-          [](uintptr_t qkv, uintptr_t kp, uintptr_t vp, uintptr_t out,
-             uintptr_t table, uintptr_t pos, int B, int H, int max_pages,
-             float scale, uintptr_t stream, bool sync, int D) {
-            launch_decode_attention_paged((void*)qkv, (void*)kp, (void*)vp,
-                                          (void*)out, (void*)table,
-                                          (void*)pos, B, H, max_pages,
-                                          scale, as_stream(stream), D);
-            if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
-          },
-          py::arg("qkv"), py::arg("kpool"), py::arg("vpool"), py::arg("out"),
-          py::arg("table"), py::arg("pos"), py::arg("B"), py::arg("H"),
-          py::arg("max_pages"), py::arg("scale"), py::arg("stream") = 0,
-          py::arg("sync") = true, py::arg("D") = 64);
+          py::arg("H"), py::arg("rows"), py::arg("smax"), py::arg("pos") = 0,
+          py::arg("table") = 0, py::arg("max_pages") = 0,
+          py::arg("stream") = 0, py::arg("sync") = true, py::arg("D") = 64);
   ops.def("decode_attention",
           [](uintptr_t qkv, uintptr_t kc, uintptr_t vc, uintptr_t out,
-             uintptr_t pos, int B, int H, int smax, float scale,
-             uintptr_t stream, bool sync, int D) {
+             uintptr_t pos, int B, int H, int rows, int smax, float scale,
+             uintptr_t table, int max_pages, uintptr_t stream, bool sync,
+             int D) {
             launch_decode_attention((void*)qkv, (void*)kc, (void*)vc,
-                                    (void*)out, (void*)pos, B, H, smax,
-                                    scale, as_stream(stream), D);
+                                    (void*)out, (void*)pos, (void*)table,
+                                    max_pages, B, H, rows, smax, scale,
+                                    as_stream(stream), D);
             if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
           },
           py::arg("qkv"), py::arg("kcache"), py::arg("vcache"),
           py::arg("out"), py::arg("pos"), py::arg("B"), py::arg("H"),
-          py::arg("smax"), py::arg("scale"), py::arg("stream") = 0,
-          py::arg("sync") = true, py::arg("D") = 64);
+          py::arg("rows"), py::arg("smax"), py::arg("scale"),
+          py::arg("table") = 0, py::arg("max_pages") = 0,
+          py::arg("stream") = 0, py::arg("sync") = true, py::arg("D") = 64);
   ops.def("decode_embed",
           [](uintptr_t ids, uintptr_t tok, uintptr_t pe, uintptr_t out,
-             uintptr_t pos, int B, int hidden, uintptr_t stream, bool sync) {
+             uintptr_t pos, int B, int rows, int smax, int hidden,
+             uintptr_t stream, bool sync) {
             launch_decode_embed((void*)ids, (void*)tok, (void*)pe, (void*)out,
-                                (void*)pos, B, hidden, as_stream(stream));
+                                (void*)pos, B, rows, smax, hidden,
+                                as_stream(stream));
             if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
           },
           py::arg("ids"), py::arg("tok"), py::arg("posemb"), py::arg("out"),
-          py::arg("pos"), py::arg("B"), py::arg("hidden"),
-          py::arg("stream") = 0, py::arg("sync") = true);
+          py::arg("pos"), py::arg("B"), py::arg("rows"), py::arg("smax"),
+          py::arg("hidden"), py::arg("stream") = 0, py::arg("sync") = true);
   ops.def("decode_gemm_fused",
           [](int pro, int epi, uintptr_t x, uintptr_t r, uintptr_t h_out,
              uintptr_t gamma, uintptr_t beta, uintptr_t Bw, uintptr_t bias,
@@ -793,44 +718,6 @@ PYBIND11_MODULE(_C, m) {
           py::arg("M") = 0, py::arg("N") = 0, py::arg("K") = 0,
           py::arg("heads") = 0, py::arg("smax") = 0, py::arg("eps") = 1e-5f,
           py::arg("stream") = 0, py::arg("sync") = true);
-  ops.def("kv_append_chunk",
-          [](uintptr_t qkv, uintptr_t kc, uintptr_t vc, uintptr_t pos, int B,
-             int H, int K, int smax, uintptr_t stream, bool sync, int D) {
-            launch_kv_append_chunk((void*)qkv, (void*)kc, (void*)vc,
-                                   (void*)pos, B, H, K, smax,
-                                   as_stream(stream), D);
-            if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
-          },
-          py::arg("qkv"), py::arg("kcache"), py::arg("vcache"),
-          py::arg("pos"), py::arg("B"), py::arg("H"), py::arg("K"),
-          py::arg("smax"), py::arg("stream") = 0, py::arg("sync") = true,
-          py::arg("D") = 64);
-  ops.def("chunk_attention",
-          [](uintptr_t qkv, uintptr_t kc, uintptr_t vc, uintptr_t out,
-             uintptr_t pos, int B, int H, int K, int smax, float scale,
-             uintptr_t stream, bool sync, int D) {
-            launch_chunk_attention((void*)qkv, (void*)kc, (void*)vc,
-                                   (void*)out, (void*)pos, B, H, K, smax,
-                                   scale, as_stream(stream), D);
-            if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
-          },
-          py::arg("qkv"), py::arg("kcache"), py::arg("vcache"),
-          py::arg("out"), py::arg("pos"), py::arg("B"), py::arg("H"),
-          py::arg("K"), py::arg("smax"), py::arg("scale"),
-          py::arg("stream") = 0, py::arg("sync") = true,
-          py::arg("D") = 64);
-  ops.def("chunk_embed",
-          [](uintptr_t ids, uintptr_t tok, uintptr_t pe, uintptr_t out,
-             uintptr_t pos, int B, int K, int smax, int hidden,
-             uintptr_t stream, bool sync) {
-            launch_chunk_embed((void*)ids, (void*)tok, (void*)pe, (void*)out,
-                               (void*)pos, B, K, smax, hidden,
-                               as_stream(stream));
-            if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
-          },
-          py::arg("ids"), py::arg("tok"), py::arg("posemb"), py::arg("out"),
-          py::arg("pos"), py::arg("B"), py::arg("K"), py::arg("smax"),
-          py::arg("hidden"), py::arg("stream") = 0, py::arg("sync") = true);
   ops.def("advance_pos", [](uintptr_t pos, int B, int smax, uintptr_t stream,
                             bool sync) {
     launch_advance_pos((void*)pos, B, smax, as_stream(stream));

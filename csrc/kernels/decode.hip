@@ -10,233 +10,142 @@
 // other slots keep decoding). advance_pos bumps every slot at the end of
 // the captured step.
 //
-// Idle-slot masking: pos[b] < 0 marks slot b IDLE — every per-slot kernel
-// early-exits for it (no cache writes, no attention scan, position stays
-// parked), so empty slots in a continuous batch cost ~nothing while the
-// captured graph keeps its fixed shape.
+// One kernel body each for the K/V scatter, the single-query attention
+// and the embedding. Two axes select the variant:
+//   rows — query/source rows per slot, b-major then row: 1 for a decode
+//          step, K for a speculative-verification chunk (row q of slot b
+//          sits at position pos[b] + q), P for a prefill range (pos is
+//          null: base position 0).
+//   KV   — cache layout policy (DenseKV / PagedKV below), the only code
+//          that knows how row t of (slot, head) is addressed.
 //
-// Cache layout per layer: K and V as [B][H][Smax][64] fp16 (contiguous
-// 128-B rows per key — one cacheline).
+// Bounds rule (every kernel here, both layouts):
+//   * pos[b] < 0 marks slot b IDLE: the block exits — no cache write, no
+//     scan, no output, position stays parked — so empty slots in a
+//     continuous batch cost ~nothing while the graph keeps its shape.
+//     A null pos (range append) has no idle slots.
+//   * a write position is clamped to smax-1; the attended length n is
+//     clamped to smax (<= 4096, the LDS score buffer — launcher-checked).
+//     Clamped rows pile up on position smax-1, which is rewritten by a
+//     later step before it is ever attended.
+//   * a paged row whose page is unmapped (table entry < 0, or logical
+//     page >= max_pages) is skipped on append. Attention does not test
+//     it: the host maps every page below pos[b] + rows before launch.
+//   smax is the session's position bound for both layouts, NOT
+//   max_pages*64: a shared pool may be larger than one session's window.
 #include "gemm_common.h"
 
 namespace trtlab {
 
-// Scatter this step's K/V head rows from the fused qkv projection output
-// (qkv [B, 3*H*64], one row per sequence) into the caches at `pos`.
+// Dense cache, per layer: K and V as [B][H][smax][D] fp16 (a key's head
+// row is contiguous — one 128-B cacheline at D = 64).
+struct DenseKV {
+  int smax;
+  __device__ int64_t row(int b, int h, int H, int D, int t) const {
+    return (((int64_t)b * H + h) * smax + t) * D;
+  }
+};
+
+// Paged cache (vLLM-style block tables): many sessions share ONE fixed
+// physical pool per layer; each slot maps logical 64-position pages to
+// physical page ids through a device table [B][max_pages] (filled by the
+// host as positions grow; reset/idle returns pages to the host free list,
+// so parked slots hold no memory). Pool layout [page][64][H][D] — a
+// position's per-head row stays contiguous. row() is negative when the
+// page is unmapped: a negative page id makes the whole offset negative
+// ((page*64 + t%64)*H + h < 0 for h < H), so the read path pays no test;
+// the table index is clamped so the lookup itself stays in bounds.
+struct PagedKV {
+  const int* table;
+  int max_pages;
+  __device__ int64_t row(int b, int h, int H, int D, int t) const {
+    int lp = t >> 6;
+    int page = table[b * max_pages + min(lp, max_pages - 1)];
+    if (lp >= max_pages) page = -1;
+    return (((int64_t)page * 64 + (t & 63)) * H + h) * D;
+  }
+};
+
+// Scatter K/V head rows from the fused qkv projection output (qkv
+// [B*rows, 3*H*D]) into the cache at position (pos ? pos[b] : 0) + q.
+// One block per (b, h, q).
+template <class KV>
 __global__ __launch_bounds__(64) void kv_append_kernel(
     const _Float16* __restrict__ qkv, _Float16* __restrict__ kcache,
-    _Float16* __restrict__ vcache, const int* __restrict__ pos, int B, int H,
-    int smax, int D) {
-  int b = blockIdx.x / H, h = blockIdx.x % H;
-  int p = pos[b];
-  if (p < 0) return;  // idle slot
+    _Float16* __restrict__ vcache, const int* __restrict__ pos, KV kv, int H,
+    int rows, int smax, int D) {
+  int q = blockIdx.x % rows;
+  int bh = blockIdx.x / rows;
+  int b = bh / H, h = bh % H;
+  int p = q;
+  if (pos) {
+    int p0 = pos[b];
+    if (p0 < 0) return;  // idle slot
+    p += p0;
+  }
+  if (p >= smax) p = smax - 1;
+  int64_t dst = kv.row(b, h, H, D, p);
+  if (dst < 0) return;  // unmapped page (host error) — fail soft, not wild
   int hid = H * D;
+  int64_t src = ((int64_t)b * rows + q) * 3 * hid + h * D;
   for (int d = threadIdx.x; d < D; d += 64) {
-    int64_t src = (int64_t)b * 3 * hid + h * D + d;
-    int64_t dst = (((int64_t)b * H + h) * smax + p) * D + d;
-    kcache[dst] = qkv[src + hid];
-    vcache[dst] = qkv[src + 2 * hid];
+    kcache[dst + d] = qkv[src + hid + d];
+    vcache[dst + d] = qkv[src + 2 * hid + d];
   }
 }
 
 void launch_kv_append(const void* qkv, void* kcache, void* vcache,
-                      const void* pos, int B, int H, int smax,
-                      hipStream_t stream, int D) {
-  hipLaunchKernelGGL(kv_append_kernel, dim3(B * H), dim3(64), 0, stream,
-                     (const _Float16*)qkv, (_Float16*)kcache,
-                     (_Float16*)vcache, (const int*)pos, B, H, smax, D);
+                      const void* pos, const void* table, int max_pages,
+                      int B, int H, int rows, int smax, hipStream_t stream,
+                      int D) {
+  if (rows < 1) throw std::runtime_error("kv_append: rows < 1");
+  auto L = [&](auto kv) {
+    hipLaunchKernelGGL(kv_append_kernel<decltype(kv)>, dim3(B * H * rows),
+                       dim3(64), 0, stream, (const _Float16*)qkv,
+                       (_Float16*)kcache, (_Float16*)vcache, (const int*)pos,
+                       kv, H, rows, smax, D);
+  };
+  if (table) L(PagedKV{(const int*)table, max_pages});
+  else L(DenseKV{smax});
 }
 
-// Batch-scatter a full prompt's K/V head rows (qkv [B*P, 3*H*64], rows
-// ordered b-major then position) into the caches at positions [0, P).
-// Grid B*H*P; fused prefill runs the prompt through the full-sequence
-// kernels once, then decode continues from position P.
-__global__ __launch_bounds__(64) void kv_append_range_kernel(
-    const _Float16* __restrict__ qkv, _Float16* __restrict__ kcache,
-    _Float16* __restrict__ vcache, int B, int H, int P, int smax, int D) {
-  int p = blockIdx.x % P;
-  int bh = blockIdx.x / P;
-  int b = bh / H, h = bh % H;
-  int hid = H * D;
-  for (int d = threadIdx.x; d < D; d += 64) {
-    int64_t src = ((int64_t)b * P + p) * 3 * hid + h * D + d;
-    int64_t dst = (((int64_t)b * H + h) * smax + p) * D + d;
-    kcache[dst] = qkv[src + hid];
-    vcache[dst] = qkv[src + 2 * hid];
-  }
-}
-
-void launch_kv_append_range(const void* qkv, void* kcache, void* vcache,
-                            int B, int H, int P, int smax,
-                            hipStream_t stream, int D) {
-  hipLaunchKernelGGL(kv_append_range_kernel, dim3(B * H * P), dim3(64), 0,
-                     stream, (const _Float16*)qkv, (_Float16*)kcache,
-                     (_Float16*)vcache, B, H, P, smax, D);
-}
-
-// Single-query attention against the cache: out[b, h*64+d] =
-// softmax(q . K[0..pos]) @ V[0..pos]. One wave per (b, h); each lane owns
-// keys lane, lane+64, ... for the score pass (its K rows are whole
-// 128-byte cachelines), then output element d = lane for the PV pass with
-// the probabilities broadcast through LDS. Smax <= 4096.
-template <int D>  // head_dim 64 or 128
+// Single-query attention against the cache: query row (b, q) attends keys
+// 0 .. pos[b]+q (its own K already appended), out[(b*rows+q), h*D+d] =
+// softmax(q . K) @ V. One wave per (b, h, q) — a chunk's queries are
+// causal within the chunk by construction of their lengths. Each lane
+// owns keys lane, lane+64, ... for the score pass (its K rows are whole
+// cachelines), then output element d = lane (+64) for the PV pass with
+// the probabilities broadcast through LDS.
+template <int D, class KV>  // head_dim 64 or 128
 __global__ __launch_bounds__(64) void decode_attention_kernel(
     const _Float16* __restrict__ qkv, const _Float16* __restrict__ kcache,
     const _Float16* __restrict__ vcache, _Float16* __restrict__ out,
-    const int* __restrict__ pos, int B, int H, int smax, float scale) {
-  __shared__ float p_s[4096];
-  int b = blockIdx.x / H, h = blockIdx.x % H;
-  int lane = threadIdx.x;
-  int hid = H * D;
-  if (pos[b] < 0) return;  // idle slot: no scan, stale output row unused
-  int n = pos[b] + 1;  // keys 0..pos[b] (this step's K already appended)
-
-  // q for this head (fp16 registers: D=128 stays within budget)
-  _Float16 q[D];
-  {
-    const _Float16* qrow = qkv + (int64_t)b * 3 * hid + h * D;
-#pragma unroll
-    for (int c = 0; c < D / 8; ++c)
-      *(half8v*)(q + c * 8) = *(const half8v*)(qrow + c * 8);
-  }
-  const _Float16* K = kcache + ((int64_t)b * H + h) * smax * D;
-  const _Float16* V = vcache + ((int64_t)b * H + h) * smax * D;
-
-  // scores for this lane's keys
-  float m = -3.0e38f;
-  for (int t = lane; t < n; t += 64) {
-    const _Float16* krow = K + (int64_t)t * D;
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < D / 8; ++c) {
-      half8v v = *(const half8v*)(krow + c * 8);
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        s += (float)q[c * 8 + j] * (float)((const _Float16*)&v)[j];
-    }
-    s *= scale;
-    p_s[t] = s;
-    m = fmaxf(m, s);
-  }
-#pragma unroll
-  for (int off = 32; off; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-  __syncthreads();
-  float l = 0.f;
-  for (int t = lane; t < n; t += 64) {
-    float e = __expf(p_s[t] - m);
-    p_s[t] = e;
-    l += e;
-  }
-#pragma unroll
-  for (int off = 32; off; off >>= 1) l += __shfl_xor(l, off, 64);
-  __syncthreads();
-
-  // PV: output elements d = lane (+64 for D=128)
-  float acc[D / 64];
-#pragma unroll
-  for (int j = 0; j < D / 64; ++j) acc[j] = 0.f;
-  for (int t = 0; t < n; ++t) {
-    const _Float16* vrow = V + (int64_t)t * D;
-    float p = p_s[t];
-#pragma unroll
-    for (int j = 0; j < D / 64; ++j)
-      acc[j] += p * (float)vrow[j * 64 + lane];
-  }
-#pragma unroll
-  for (int j = 0; j < D / 64; ++j)
-    out[(int64_t)b * hid + h * D + j * 64 + lane] =
-        (_Float16)(acc[j] / l);
-}
-
-void launch_decode_attention(const void* qkv, const void* kcache,
-                             const void* vcache, void* out, const void* pos,
-                             int B, int H, int smax, float scale,
-                             hipStream_t stream, int D) {
-  if (smax > 4096)
-    throw std::runtime_error("decode_attention: smax > 4096 unsupported");
-  if (D == 128)
-    hipLaunchKernelGGL(decode_attention_kernel<128>, dim3(B * H), dim3(64),
-                       0, stream, (const _Float16*)qkv,
-                       (const _Float16*)kcache, (const _Float16*)vcache,
-                       (_Float16*)out, (const int*)pos, B, H, smax, scale);
-  else if (D == 64)
-    hipLaunchKernelGGL(decode_attention_kernel<64>, dim3(B * H), dim3(64), 0,
-                       stream, (const _Float16*)qkv, (const _Float16*)kcache,
-                       (const _Float16*)vcache, (_Float16*)out,
-                       (const int*)pos, B, H, smax, scale);
-  else
-    throw std::runtime_error("decode_attention: head_dim must be 64 or 128");
-}
-
-// ---- speculative-decoding verification chunk kernels ----
-// The draft model proposes K tokens; the target verifies them in ONE
-// chunked forward instead of K sequential replays. Rows are b-major then
-// chunk position: row r = b*K + q corresponds to absolute position
-// pos[b] + q.
-
-// Scatter a chunk's K/V head rows into the caches at pos[b] + q.
-__global__ __launch_bounds__(64) void kv_append_chunk_kernel(
-    const _Float16* __restrict__ qkv, _Float16* __restrict__ kcache,
-    _Float16* __restrict__ vcache, const int* __restrict__ pos, int B, int H,
-    int K, int smax, int D) {
-  int q = blockIdx.x % K;
-  int bh = blockIdx.x / K;
-  int b = bh / H, h = bh % H;
-  int p0 = pos[b];
-  if (p0 < 0) return;  // idle slot
-  int p = p0 + q;
-  if (p >= smax) p = smax - 1;
-  int hid = H * D;
-  for (int d = threadIdx.x; d < D; d += 64) {
-    int64_t src = ((int64_t)b * K + q) * 3 * hid + h * D + d;
-    int64_t dst = (((int64_t)b * H + h) * smax + p) * D + d;
-    kcache[dst] = qkv[src + hid];
-    vcache[dst] = qkv[src + 2 * hid];
-  }
-}
-
-void launch_kv_append_chunk(const void* qkv, void* kcache, void* vcache,
-                            const void* pos, int B, int H, int K, int smax,
-                            hipStream_t stream, int D) {
-  hipLaunchKernelGGL(kv_append_chunk_kernel, dim3(B * H * K), dim3(64), 0,
-                     stream, (const _Float16*)qkv, (_Float16*)kcache,
-                     (_Float16*)vcache, (const int*)pos, B, H, K, smax, D);
-}
-
-// Multi-query single-head attention against the cache: query row (b, q)
-// attends keys 0 .. pos[b]+q (its own K already appended). One wave per
-// (b, q, h) — the chunk's queries are causal within the chunk by
-// construction of their lengths.
-template <int D>  // head_dim 64 or 128
-__global__ __launch_bounds__(64) void chunk_attention_kernel(
-    const _Float16* __restrict__ qkv, const _Float16* __restrict__ kcache,
-    const _Float16* __restrict__ vcache, _Float16* __restrict__ out,
-    const int* __restrict__ pos, int B, int H, int K, int smax,
+    const int* __restrict__ pos, KV kv, int H, int rows, int smax,
     float scale) {
   __shared__ float p_s[4096];
-  int q = blockIdx.x % K;
-  int bh = blockIdx.x / K;
+  int q = blockIdx.x % rows;
+  int bh = blockIdx.x / rows;
   int b = bh / H, h = bh % H;
   int lane = threadIdx.x;
   int hid = H * D;
   int p0 = pos[b];
-  if (p0 < 0) return;  // idle slot
+  if (p0 < 0) return;  // idle slot: stale output row unused
   int n = p0 + q + 1;
   if (n > smax) n = smax;
 
+  // q for this head (fp16 registers: D=128 stays within budget)
   _Float16 qv[D];
   {
-    const _Float16* qrow = qkv + ((int64_t)b * K + q) * 3 * hid + h * D;
+    const _Float16* qrow = qkv + ((int64_t)b * rows + q) * 3 * hid + h * D;
 #pragma unroll
     for (int c = 0; c < D / 8; ++c)
       *(half8v*)(qv + c * 8) = *(const half8v*)(qrow + c * 8);
   }
-  const _Float16* Kc = kcache + ((int64_t)b * H + h) * smax * D;
-  const _Float16* Vc = vcache + ((int64_t)b * H + h) * smax * D;
 
+  // scores for this lane's keys
   float m = -3.0e38f;
   for (int t = lane; t < n; t += 64) {
-    const _Float16* krow = Kc + (int64_t)t * D;
+    const _Float16* krow = kcache + kv.row(b, h, H, D, t);
     float s = 0.f;
 #pragma unroll
     for (int c = 0; c < D / 8; ++c) {
@@ -261,11 +170,13 @@ __global__ __launch_bounds__(64) void chunk_attention_kernel(
 #pragma unroll
   for (int off = 32; off; off >>= 1) l += __shfl_xor(l, off, 64);
   __syncthreads();
+
+  // PV: output elements d = lane (+64 for D=128)
   float acc[D / 64];
 #pragma unroll
   for (int j = 0; j < D / 64; ++j) acc[j] = 0.f;
   for (int t = 0; t < n; ++t) {
-    const _Float16* vrow = Vc + (int64_t)t * D;
+    const _Float16* vrow = vcache + kv.row(b, h, H, D, t);
     float p = p_s[t];
 #pragma unroll
     for (int j = 0; j < D / 64; ++j)
@@ -273,46 +184,52 @@ __global__ __launch_bounds__(64) void chunk_attention_kernel(
   }
 #pragma unroll
   for (int j = 0; j < D / 64; ++j)
-    out[((int64_t)b * K + q) * hid + h * D + j * 64 + lane] =
+    out[((int64_t)b * rows + q) * hid + h * D + j * 64 + lane] =
         (_Float16)(acc[j] / l);
 }
 
-void launch_chunk_attention(const void* qkv, const void* kcache,
-                            const void* vcache, void* out, const void* pos,
-                            int B, int H, int K, int smax, float scale,
-                            hipStream_t stream, int D) {
+void launch_decode_attention(const void* qkv, const void* kcache,
+                             const void* vcache, void* out, const void* pos,
+                             const void* table, int max_pages, int B, int H,
+                             int rows, int smax, float scale,
+                             hipStream_t stream, int D) {
   if (smax > 4096)
-    throw std::runtime_error("chunk_attention: smax > 4096 unsupported");
-  if (D == 128)
-    hipLaunchKernelGGL(chunk_attention_kernel<128>, dim3(B * H * K),
-                       dim3(64), 0, stream, (const _Float16*)qkv,
-                       (const _Float16*)kcache, (const _Float16*)vcache,
-                       (_Float16*)out, (const int*)pos, B, H, K, smax,
-                       scale);
-  else if (D == 64)
-    hipLaunchKernelGGL(chunk_attention_kernel<64>, dim3(B * H * K), dim3(64),
-                       0, stream, (const _Float16*)qkv,
-                       (const _Float16*)kcache, (const _Float16*)vcache,
-                       (_Float16*)out, (const int*)pos, B, H, K, smax,
-                       scale);
-  else
-    throw std::runtime_error("chunk_attention: head_dim must be 64 or 128");
+    throw std::runtime_error("decode_attention: smax > 4096 unsupported");
+  if (D != 64 && D != 128)
+    throw std::runtime_error("decode_attention: head_dim must be 64 or 128");
+  if (rows < 1) throw std::runtime_error("decode_attention: rows < 1");
+  auto L = [&](auto d_c, auto kv) {
+    hipLaunchKernelGGL(
+        (decode_attention_kernel<decltype(d_c)::value, decltype(kv)>),
+        dim3(B * H * rows), dim3(64), 0, stream, (const _Float16*)qkv,
+        (const _Float16*)kcache, (const _Float16*)vcache, (_Float16*)out,
+        (const int*)pos, kv, H, rows, smax, scale);
+  };
+  using D64 = std::integral_constant<int, 64>;
+  using D128 = std::integral_constant<int, 128>;
+  PagedKV paged{(const int*)table, max_pages};
+  DenseKV dense{smax};
+  if (table && D == 128) L(D128{}, paged);
+  else if (table) L(D64{}, paged);
+  else if (D == 128) L(D128{}, dense);
+  else L(D64{}, dense);
 }
 
-// Chunk embedding: out[b*K + q] = tok[ids[b*K + q]] + posemb[pos[b] + q].
-__global__ void chunk_embed_kernel(const int* __restrict__ ids,
-                                   const _Float16* __restrict__ tok,
-                                   const _Float16* __restrict__ posemb,
-                                   _Float16* __restrict__ out,
-                                   const int* __restrict__ pos, int K,
-                                   int smax, int hidden) {
-  int q = blockIdx.x % K;
-  int b = blockIdx.x / K;
+// Token + position embedding: out[b*rows + q] = tok[ids[b*rows + q]] +
+// posemb[pos[b] + q].
+__global__ void decode_embed_kernel(const int* __restrict__ ids,
+                                    const _Float16* __restrict__ tok,
+                                    const _Float16* __restrict__ posemb,
+                                    _Float16* __restrict__ out,
+                                    const int* __restrict__ pos, int rows,
+                                    int smax, int hidden) {
+  int q = blockIdx.x % rows;
+  int b = blockIdx.x / rows;
   int p0 = pos[b];
-  if (p0 < 0) return;
+  if (p0 < 0) return;  // idle slot
   int p = p0 + q;
   if (p >= smax) p = smax - 1;
-  int64_t r = (int64_t)b * K + q;
+  int64_t r = (int64_t)b * rows + q;
   int64_t t = (int64_t)ids[r] * hidden;
   for (int i = threadIdx.x; i < hidden; i += blockDim.x)
     out[r * hidden + i] =
@@ -320,38 +237,14 @@ __global__ void chunk_embed_kernel(const int* __restrict__ ids,
                    (float)posemb[(int64_t)p * hidden + i]);
 }
 
-void launch_chunk_embed(const void* ids, const void* tok, const void* posemb,
-                        void* out, const void* pos, int B, int K, int smax,
-                        int hidden, hipStream_t stream) {
-  hipLaunchKernelGGL(chunk_embed_kernel, dim3(B * K), dim3(256), 0, stream,
-                     (const int*)ids, (const _Float16*)tok,
-                     (const _Float16*)posemb, (_Float16*)out,
-                     (const int*)pos, K, smax, hidden);
-}
-
-// Token + position embedding for one decode step: out[b] =
-// tok[ids[b]] + posemb[pos]. ids are this step's B tokens.
-__global__ void decode_embed_kernel(const int* __restrict__ ids,
-                                    const _Float16* __restrict__ tok,
-                                    const _Float16* __restrict__ posemb,
-                                    _Float16* __restrict__ out,
-                                    const int* __restrict__ pos, int hidden) {
-  int b = blockIdx.x;
-  int p = pos[b];
-  if (p < 0) return;  // idle slot
-  int64_t t = (int64_t)ids[b] * hidden;
-  for (int i = threadIdx.x; i < hidden; i += blockDim.x)
-    out[(int64_t)b * hidden + i] =
-        (_Float16)((float)tok[t + i] + (float)posemb[(int64_t)p * hidden + i]);
-}
-
 void launch_decode_embed(const void* ids, const void* tok, const void* posemb,
-                         void* out, const void* pos, int B, int hidden,
-                         hipStream_t stream) {
-  hipLaunchKernelGGL(decode_embed_kernel, dim3(B), dim3(256), 0, stream,
-                     (const int*)ids, (const _Float16*)tok,
-                     (const _Float16*)posemb, (_Float16*)out, (const int*)pos,
-                     hidden);
+                         void* out, const void* pos, int B, int rows,
+                         int smax, int hidden, hipStream_t stream) {
+  if (rows < 1) throw std::runtime_error("decode_embed: rows < 1");
+  hipLaunchKernelGGL(decode_embed_kernel, dim3(B * rows), dim3(256), 0,
+                     stream, (const int*)ids, (const _Float16*)tok,
+                     (const _Float16*)posemb, (_Float16*)out,
+                     (const int*)pos, rows, smax, hidden);
 }
 
 // Advance every slot's position counter (last node of the captured
@@ -513,13 +406,9 @@ __global__ __launch_bounds__(256) void decode_gemm_fused_kernel(
       int idx = c * 256 + tid;
       int row = idx >> 3;
       int cb = (idx & 7) * 16;
-      int kk = (cb / 2);  // column within the tile for gamma/beta lookup
-      (void)kk;
       float mean = sm_mean[row < M ? row : M - 1];
       float inv = sm_inv[row < M ? row : M - 1];
       _Float16 o8[8];
-      int kcol = 0;  // filled below per element
-      (void)kcol;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         int kg = cur_kbase + cb / 2 + j;
@@ -617,284 +506,6 @@ void launch_decode_gemm_fused(int pro, int epi, const void* x, const void* r,
   else if (pro == 3 && epi == 2) L(I3{}, E2{});
   else if (pro == 3 && epi == 0) L(I3{}, E0{});
   else throw std::runtime_error("decode_gemm_fused: bad pro/epi combo");
-}
-
-
-// ---- paged KV cache (vLLM-style block tables) ----
-// Many concurrent sessions share ONE fixed physical pool per layer; each
-// slot maps logical 64-position pages to physical page ids through a
-// device block table [B][max_pages] (filled by the host as positions
-// grow; reset/idle returns pages to the host free list, so parked slots
-// hold no memory). Page layout: [page][64 positions][H][64] — a
-// position's per-head row stays one contiguous 128-B cacheline.
-__global__ __launch_bounds__(64) void kv_append_paged_kernel(
-    const _Float16* __restrict__ qkv, _Float16* __restrict__ kpool,
-    _Float16* __restrict__ vpool, const int* __restrict__ table,
-    const int* __restrict__ pos, int B, int H, int max_pages, int D) {
-  int b = blockIdx.x / H, h = blockIdx.x % H;
-  int p = pos[b];
-  if (p < 0) return;  // idle slot
-  int page = table[b * max_pages + (p >> 6)];
-  if (page < 0) return;  // unmapped (host error) — fail soft, not wild
-  int hid = H * D;
-  for (int d = threadIdx.x; d < D; d += 64) {
-    int64_t src = (int64_t)b * 3 * hid + h * D + d;
-    int64_t dst = (((int64_t)page * 64 + (p & 63)) * H + h) * D + d;
-    kpool[dst] = qkv[src + hid];
-    vpool[dst] = qkv[src + 2 * hid];
-  }
-}
-
-// ---- paged variants of the chunk / prefill cache writers + reader ----
-// (speculative verification and fused prefill for paged sessions: same
-// math as the dense chunk kernels, addresses resolved through the
-// per-slot page table; pages host-mapped before launch.)
-__global__ __launch_bounds__(64) void kv_append_chunk_paged_kernel(
-    const _Float16* __restrict__ qkv, _Float16* __restrict__ kpool,
-    _Float16* __restrict__ vpool, const int* __restrict__ table,
-    const int* __restrict__ pos, int B, int H, int K, int max_pages,
-    int D) {
-  int q = blockIdx.x % K;
-  int bh = blockIdx.x / K;
-  int b = bh / H, h = bh % H;
-  int p0 = pos[b];
-  if (p0 < 0) return;  // idle slot
-  int p = p0 + q;
-  int page = table[b * max_pages + (p >> 6)];
-  if (page < 0) return;  // unmapped (host error) — fail soft
-  int hid = H * D;
-  for (int d = threadIdx.x; d < D; d += 64) {
-    int64_t src = ((int64_t)b * K + q) * 3 * hid + h * D + d;
-    int64_t dst = (((int64_t)page * 64 + (p & 63)) * H + h) * D + d;
-    kpool[dst] = qkv[src + hid];
-    vpool[dst] = qkv[src + 2 * hid];
-  }
-}
-
-void launch_kv_append_chunk_paged(const void* qkv, void* kpool, void* vpool,
-                                  const void* table, const void* pos, int B,
-                                  int H, int K, int max_pages,
-                                  hipStream_t stream, int D) {
-  hipLaunchKernelGGL(kv_append_chunk_paged_kernel, dim3(B * H * K),
-                     dim3(64), 0, stream, (const _Float16*)qkv,
-                     (_Float16*)kpool, (_Float16*)vpool, (const int*)table,
-                     (const int*)pos, B, H, K, max_pages, D);
-}
-
-__global__ __launch_bounds__(64) void kv_append_range_paged_kernel(
-    const _Float16* __restrict__ qkv, _Float16* __restrict__ kpool,
-    _Float16* __restrict__ vpool, const int* __restrict__ table, int B,
-    int H, int P, int max_pages, int D) {
-  int p = blockIdx.x % P;
-  int bh = blockIdx.x / P;
-  int b = bh / H, h = bh % H;
-  int page = table[b * max_pages + (p >> 6)];
-  if (page < 0) return;
-  int hid = H * D;
-  for (int d = threadIdx.x; d < D; d += 64) {
-    int64_t src = ((int64_t)b * P + p) * 3 * hid + h * D + d;
-    int64_t dst = (((int64_t)page * 64 + (p & 63)) * H + h) * D + d;
-    kpool[dst] = qkv[src + hid];
-    vpool[dst] = qkv[src + 2 * hid];
-  }
-}
-
-void launch_kv_append_range_paged(const void* qkv, void* kpool, void* vpool,
-                                  const void* table, int B, int H, int P,
-                                  int max_pages, hipStream_t stream, int D) {
-  hipLaunchKernelGGL(kv_append_range_paged_kernel, dim3(B * H * P),
-                     dim3(64), 0, stream, (const _Float16*)qkv,
-                     (_Float16*)kpool, (_Float16*)vpool, (const int*)table,
-                     B, H, P, max_pages, D);
-}
-
-template <int D>  // head_dim 64 or 128
-__global__ __launch_bounds__(64) void chunk_attention_paged_kernel(
-    const _Float16* __restrict__ qkv, const _Float16* __restrict__ kpool,
-    const _Float16* __restrict__ vpool, _Float16* __restrict__ out,
-    const int* __restrict__ table, const int* __restrict__ pos, int B,
-    int H, int K, int max_pages, float scale) {
-  __shared__ float p_s[4096];
-  int q = blockIdx.x % K;
-  int bh = blockIdx.x / K;
-  int b = bh / H, h = bh % H;
-  int lane = threadIdx.x;
-  int hid = H * D;
-  int p0 = pos[b];
-  if (p0 < 0) return;  // idle slot
-  int n = p0 + q + 1;
-
-  _Float16 qv[D];
-  {
-    const _Float16* qrow = qkv + ((int64_t)b * K + q) * 3 * hid + h * D;
-#pragma unroll
-    for (int c = 0; c < D / 8; ++c)
-      *(half8v*)(qv + c * 8) = *(const half8v*)(qrow + c * 8);
-  }
-  const int* trow = table + b * max_pages;
-
-  float m = -3.0e38f;
-  for (int t = lane; t < n; t += 64) {
-    int page = trow[t >> 6];
-    const _Float16* krow =
-        kpool + (((int64_t)page * 64 + (t & 63)) * H + h) * D;
-    float sc = 0.f;
-#pragma unroll
-    for (int c = 0; c < D / 8; ++c) {
-      half8v v = *(const half8v*)(krow + c * 8);
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        sc += (float)qv[c * 8 + j] * (float)((const _Float16*)&v)[j];
-    }
-    sc *= scale;
-    p_s[t] = sc;
-    m = fmaxf(m, sc);
-  }
-#pragma unroll
-  for (int off = 32; off; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-  __syncthreads();
-  float l = 0.f;
-  for (int t = lane; t < n; t += 64) {
-    float e = __expf(p_s[t] - m);
-    p_s[t] = e;
-    l += e;
-  }
-#pragma unroll
-  for (int off = 32; off; off >>= 1) l += __shfl_xor(l, off, 64);
-  __syncthreads();
-  float acc[D / 64];
-#pragma unroll
-  for (int j = 0; j < D / 64; ++j) acc[j] = 0.f;
-  for (int t = 0; t < n; ++t) {
-    int page = trow[t >> 6];
-    const _Float16* vrow =
-        vpool + (((int64_t)page * 64 + (t & 63)) * H + h) * D;
-    float pp = p_s[t];
-#pragma unroll
-    for (int j = 0; j < D / 64; ++j)
-      acc[j] += pp * (float)vrow[j * 64 + lane];
-  }
-#pragma unroll
-  for (int j = 0; j < D / 64; ++j)
-    out[((int64_t)b * K + q) * hid + h * D + j * 64 + lane] =
-        (_Float16)(acc[j] / l);
-}
-
-void launch_chunk_attention_paged(const void* qkv, const void* kpool,
-                                  const void* vpool, void* out,
-                                  const void* table, const void* pos, int B,
-                                  int H, int K, int max_pages, float scale,
-                                  hipStream_t stream, int D) {
-  if (D == 128)
-    hipLaunchKernelGGL(chunk_attention_paged_kernel<128>, dim3(B * H * K),
-                       dim3(64), 0, stream, (const _Float16*)qkv,
-                       (const _Float16*)kpool, (const _Float16*)vpool,
-                       (_Float16*)out, (const int*)table, (const int*)pos,
-                       B, H, K, max_pages, scale);
-  else if (D == 64)
-    hipLaunchKernelGGL(chunk_attention_paged_kernel<64>, dim3(B * H * K),
-                       dim3(64), 0, stream, (const _Float16*)qkv,
-                       (const _Float16*)kpool, (const _Float16*)vpool,
-                       (_Float16*)out, (const int*)table, (const int*)pos,
-                       B, H, K, max_pages, scale);
-  else
-    throw std::runtime_error("chunk_attention_paged: head_dim 64/128");
-}
-
-void launch_kv_append_paged(const void* qkv, void* kpool, void* vpool,
-                            const void* table, const void* pos, int B, int H,
-                            int max_pages, hipStream_t stream, int D) {
-  hipLaunchKernelGGL(kv_append_paged_kernel, dim3(B * H), dim3(64), 0,
-                     stream, (const _Float16*)qkv, (_Float16*)kpool,
-                     (_Float16*)vpool, (const int*)table, (const int*)pos,
-                     B, H, max_pages, D);
-}
-
-template <int D>  // head_dim 64 or 128
-__global__ __launch_bounds__(64) void decode_attention_paged_kernel(
-    const _Float16* __restrict__ qkv, const _Float16* __restrict__ kpool,
-    const _Float16* __restrict__ vpool, _Float16* __restrict__ out,
-    const int* __restrict__ table, const int* __restrict__ pos, int B, int H,
-    int max_pages, float scale) {
-  __shared__ float p_s[4096];
-  int b = blockIdx.x / H, h = blockIdx.x % H;
-  int lane = threadIdx.x;
-  int hid = H * D;
-  if (pos[b] < 0) return;  // idle slot
-  int n = pos[b] + 1;
-
-  _Float16 q[D];
-  {
-    const _Float16* qrow = qkv + (int64_t)b * 3 * hid + h * D;
-#pragma unroll
-    for (int c = 0; c < D / 8; ++c)
-      *(half8v*)(q + c * 8) = *(const half8v*)(qrow + c * 8);
-  }
-  const int* tab = table + (int64_t)b * max_pages;
-
-  float m = -3.0e38f;
-  for (int t = lane; t < n; t += 64) {
-    int64_t rowoff = (((int64_t)tab[t >> 6] * 64 + (t & 63)) * H + h) * D;
-    const _Float16* krow = kpool + rowoff;
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < D / 8; ++c) {
-      half8v v = *(const half8v*)(krow + c * 8);
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        s += (float)q[c * 8 + j] * (float)((const _Float16*)&v)[j];
-    }
-    s *= scale;
-    p_s[t] = s;
-    m = fmaxf(m, s);
-  }
-#pragma unroll
-  for (int off = 32; off; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-  __syncthreads();
-  float l = 0.f;
-  for (int t = lane; t < n; t += 64) {
-    float e = __expf(p_s[t] - m);
-    p_s[t] = e;
-    l += e;
-  }
-#pragma unroll
-  for (int off = 32; off; off >>= 1) l += __shfl_xor(l, off, 64);
-  __syncthreads();
-  float acc[D / 64];
-#pragma unroll
-  for (int j = 0; j < D / 64; ++j) acc[j] = 0.f;
-  for (int t = 0; t < n; ++t) {
-    int64_t rowoff = (((int64_t)tab[t >> 6] * 64 + (t & 63)) * H + h) * D;
-    float p = p_s[t];
-#pragma unroll
-    for (int j = 0; j < D / 64; ++j)
-      acc[j] += p * (float)vpool[rowoff + j * 64 + lane];
-  }
-#pragma unroll
-  for (int j = 0; j < D / 64; ++j)
-    out[(int64_t)b * hid + h * D + j * 64 + lane] = (_Float16)(acc[j] / l);
-}
-
-void launch_decode_attention_paged(const void* qkv, const void* kpool,
-                                   const void* vpool, void* out,
-                                   const void* table, const void* pos, int B,
-                                   int H, int max_pages, float scale,
-                                   hipStream_t stream, int D) {
-  if (D == 128)
-    hipLaunchKernelGGL(decode_attention_paged_kernel<128>, dim3(B * H),
-                       dim3(64), 0, stream, (const _Float16*)qkv,
-                       (const _Float16*)kpool, (const _Float16*)vpool,
-                       (_Float16*)out, (const int*)table, (const int*)pos,
-                       B, H, max_pages, scale);
-  else if (D == 64)
-    hipLaunchKernelGGL(decode_attention_paged_kernel<64>, dim3(B * H),
-                       dim3(64), 0, stream, (const _Float16*)qkv,
-                       (const _Float16*)kpool, (const _Float16*)vpool,
-                       (_Float16*)out, (const int*)table, (const int*)pos,
-                       B, H, max_pages, scale);
-  else
-    throw std::runtime_error(
-        "decode_attention_paged: head_dim must be 64 or 128");
 }
 
 }  // namespace trtlab

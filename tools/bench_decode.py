@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""GPT-2 incremental decode micro-benchmark (KV cache + hipGraph replay)."""
+"""GPT-2 incremental decode micro-benchmark (KV cache + hipGraph replay).
+--paged times the paged-KV session (private pool sized for smax)."""
+import argparse
 import os
 import sys
 import time
@@ -13,10 +15,14 @@ from trtlab_amd.models import build_gpt2
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--paged", action="store_true")
+    args = ap.parse_args()
     for batch in (8, 64):
         g = build_gpt2(batch=batch, seq=1024, layers=12, seed=0,
                        embeddings=True)
-        sess = DecodeSession(g, batch=batch, smax=1024, capture=True)
+        sess = DecodeSession(g, batch=batch, smax=1024, capture=True,
+                             paged=args.paged)
         rng = np.random.RandomState(0)
         ids = rng.randint(1, 50257, (batch,)).astype(np.int32)
         for _ in range(20):  # warmup + capture

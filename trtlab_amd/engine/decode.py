@@ -307,8 +307,8 @@ class DecodeSession:
                                  lay["kcache"].data_ptr(),
                                  lay["vcache"].data_ptr(),
                                  self.att.data_ptr(), self.pos.data_ptr(),
-                                 B, self.heads, self.smax, scale, stream=s,
-                                 sync=False)
+                                 B, self.heads, 1, self.smax, scale,
+                                 stream=s, sync=False)
             ops.gemm_bt(0, self.att.data_ptr(), lay["proj_w"].data_ptr(),
                         self.x2.data_ptr(), bias=lay["proj_b"].data_ptr(),
                         M=B, N=Hd, K=Hd, epi=self._epi_bias, stream=s,
@@ -343,38 +343,31 @@ class DecodeSession:
         ops.advance_pos(self.pos.data_ptr(), B, self.smax, stream=s,
                         sync=False)
 
-    def _kv_attn(self, li: int, lay: Dict):
-        """Shared per-layer KV append + attention (dense or paged)."""
+    def _kv(self, li: int, lay: Dict, qkv_ptr: int, rows: int,
+            att_ptr: int = 0) -> None:
+        """Per-layer KV append of `rows` rows per slot (1 = step, K =
+        verify chunk) at pos[b] + row, then attention into att_ptr —
+        dense caches or the paged pool. att_ptr = 0 is the prefill range
+        writer: base position 0 (null pos), append only."""
         ops, s = self._C.ops, self.stream
-        B = self.batch
-        scale = 1.0 / float(np.sqrt(float(self.hd)))
         if self.kv_pool is not None:
             pool = self.kv_pool
-            ops.kv_append_paged(self.qkv.data_ptr(),
-                                pool.kpools[li].data_ptr(),
-                                pool.vpools[li].data_ptr(),
-                                pool.table.data_ptr(),
-                                self.pos.data_ptr(), B, self.heads,
-                                pool.max_pages, stream=s, sync=False,
-                                D=self.hd)
-            ops.decode_attention_paged(
-                self.qkv.data_ptr(), pool.kpools[li].data_ptr(),
-                pool.vpools[li].data_ptr(), self.att.data_ptr(),
-                pool.table.data_ptr(), self.pos.data_ptr(), B,
-                self.heads, pool.max_pages, scale, stream=s,
-                sync=False, D=self.hd)
+            kc, vc = pool.kpools[li].data_ptr(), pool.vpools[li].data_ptr()
+            table, mp = pool.table.data_ptr(), pool.max_pages
         else:
-            ops.kv_append(self.qkv.data_ptr(), lay["kcache"].data_ptr(),
-                          lay["vcache"].data_ptr(), self.pos.data_ptr(),
-                          B, self.heads, self.smax, stream=s, sync=False,
-                          D=self.hd)
-            ops.decode_attention(self.qkv.data_ptr(),
-                                 lay["kcache"].data_ptr(),
-                                 lay["vcache"].data_ptr(),
-                                 self.att.data_ptr(),
-                                 self.pos.data_ptr(), B,
-                                 self.heads, self.smax, scale,
-                                 stream=s, sync=False, D=self.hd)
+            kc, vc = lay["kcache"].data_ptr(), lay["vcache"].data_ptr()
+            table, mp = 0, 0
+        ops.kv_append(qkv_ptr, kc, vc, self.batch, self.heads, rows,
+                      self.smax, pos=self.pos.data_ptr() if att_ptr else 0,
+                      table=table, max_pages=mp, stream=s, sync=False,
+                      D=self.hd)
+        if att_ptr:
+            scale = 1.0 / float(np.sqrt(float(self.hd)))
+            ops.decode_attention(qkv_ptr, kc, vc, att_ptr,
+                                 self.pos.data_ptr(), self.batch,
+                                 self.heads, rows, self.smax, scale,
+                                 table=table, max_pages=mp, stream=s,
+                                 sync=False, D=self.hd)
 
     def _enqueue_llama(self):
         """One LLaMA decode step (pos-relative, captured like the gpt2
@@ -390,7 +383,8 @@ class DecodeSession:
         ops = C.ops
         ops.decode_embed(self.ids.data_ptr(), self.tok.data_ptr(),
                          self.posemb.data_ptr(), self.h.data_ptr(),
-                         self.pos.data_ptr(), B, Hd, stream=s, sync=False)
+                         self.pos.data_ptr(), B, 1, self.smax, Hd, stream=s,
+                         sync=False)
         ops.rmsnorm(0, self.h.data_ptr(),
                     self.layers[0]["rms1_g"].data_ptr(), self.x.data_ptr(),
                     B, Hd, eps=self.rms_eps, stream=s, sync=False)
@@ -401,7 +395,7 @@ class DecodeSession:
             ops.rope(0, self.qkv.data_ptr(), pos=self.pos.data_ptr(), M=B,
                      S=self.smax, H=self.heads, D=self.hd, theta=self.theta,
                      stream=s, sync=False)
-            self._kv_attn(li, lay)
+            self._kv(li, lay, self.qkv.data_ptr(), 1, self.att.data_ptr())
             ops.gemm_bt(0, self.att.data_ptr(), lay["proj_w"].data_ptr(),
                         self.x2.data_ptr(), M=B, N=Hd, K=Hd,
                         epi=self._epi_none, stream=s, sync=False, tile=T4)
@@ -460,7 +454,8 @@ class DecodeSession:
         ops = C.ops
         ops.decode_embed(self.ids.data_ptr(), self.tok.data_ptr(),
                          self.posemb.data_ptr(), self.h.data_ptr(),
-                         self.pos.data_ptr(), B, Hd, stream=s, sync=False)
+                         self.pos.data_ptr(), B, 1, self.smax, Hd, stream=s,
+                         sync=False)
         ops.layernorm(0, self.h.data_ptr(),
                       self.layers[0]["ln1_g"].data_ptr(),
                       self.layers[0]["ln1_b"].data_ptr(), self.x.data_ptr(),
@@ -470,7 +465,7 @@ class DecodeSession:
                         self.qkv.data_ptr(), bias=lay["qkv_b"].data_ptr(),
                         M=B, N=3 * Hd, K=Hd, epi=self._epi_bias, stream=s,
                         sync=False, tile=T4)
-            self._kv_attn(li, lay)
+            self._kv(li, lay, self.qkv.data_ptr(), 1, self.att.data_ptr())
             ops.gemm_bt(0, self.att.data_ptr(), lay["proj_w"].data_ptr(),
                         self.x2.data_ptr(), bias=lay["proj_b"].data_ptr(),
                         M=B, N=Hd, K=Hd, epi=self._epi_bias, stream=s,
@@ -506,23 +501,6 @@ class DecodeSession:
         ops.advance_pos(self.pos.data_ptr(), B, self.smax, stream=s,
                         sync=False)
 
-    def _kv_range(self, li: int, lay: Dict, qkv_ptr: int, B: int,
-                  Pp: int) -> None:
-        """Prefill cache writer (dense or paged)."""
-        ops, s = self._C.ops, self.stream
-        if self.kv_pool is not None:
-            pool = self.kv_pool
-            ops.kv_append_range_paged(qkv_ptr, pool.kpools[li].data_ptr(),
-                                      pool.vpools[li].data_ptr(),
-                                      pool.table.data_ptr(), B, self.heads,
-                                      Pp, pool.max_pages, stream=s,
-                                      sync=False, D=self.hd)
-        else:
-            ops.kv_append_range(qkv_ptr, lay["kcache"].data_ptr(),
-                                lay["vcache"].data_ptr(), B, self.heads,
-                                Pp, self.smax, stream=s, sync=False,
-                                D=self.hd)
-
     def prefill(self, prompt: np.ndarray) -> np.ndarray:
         """Fill the KV caches from a whole prompt [B, P] in ONE pass through
         the full-sequence kernels (causal online-softmax attention), then
@@ -550,7 +528,7 @@ class DecodeSession:
         ids[:, :P] = prompt
         if self.kv_pool is not None:
             # map pages covering the PADDED prompt (the tail rows are
-            # written by kv_append_range_paged and overwritten by later
+            # written by the range kv_append and overwritten by later
             # decode steps before they are ever attended)
             for b in range(B):
                 for li in range((Pp - 1) // 64 + 1):
@@ -585,7 +563,7 @@ class DecodeSession:
                 # padded tail is causal-masked / overwritten before read)
                 ops.rope(0, qkv.data_ptr(), M=M, S=Pp, H=self.heads,
                          D=self.hd, theta=self.theta, stream=s, sync=False)
-                self._kv_range(li, lay, qkv.data_ptr(), B, Pp)
+                self._kv(li, lay, qkv.data_ptr(), Pp)
                 ops.attention(0, qkv.data_ptr(), x2.data_ptr(), B, Pp,
                               self.heads, self.hd, scale, stream=s,
                               sync=False, causal=1)
@@ -623,7 +601,7 @@ class DecodeSession:
                             qkv.data_ptr(), bias=lay["qkv_b"].data_ptr(),
                             M=M, N=3 * Hd, K=Hd, epi=self._epi_bias,
                             stream=s, sync=False)
-                self._kv_range(li, lay, qkv.data_ptr(), B, Pp)
+                self._kv(li, lay, qkv.data_ptr(), Pp)
                 ops.attention(0, qkv.data_ptr(), x2.data_ptr(), B, Pp,
                               self.heads, self.hd, scale,
                               stream=s, sync=False, causal=1)
@@ -721,42 +699,6 @@ class DecodeSession:
                 if self.logits is not None else out)
 
     # ------------------------------------------- speculative verification
-    def _kv_attn_chunk(self, li: int, lay: Dict, cb: Dict, B: int,
-                       K: int) -> None:
-        """Per-layer chunk KV append + multi-query attention (dense or
-        paged — the paged path resolves rows through the page table)."""
-        ops, s = self._C.ops, self.stream
-        scale = 1.0 / float(np.sqrt(float(self.hd)))
-        if self.kv_pool is not None:
-            pool = self.kv_pool
-            ops.kv_append_chunk_paged(cb["qkv"].data_ptr(),
-                                      pool.kpools[li].data_ptr(),
-                                      pool.vpools[li].data_ptr(),
-                                      pool.table.data_ptr(),
-                                      self.pos.data_ptr(), B, self.heads,
-                                      K, pool.max_pages, stream=s,
-                                      sync=False, D=self.hd)
-            ops.chunk_attention_paged(cb["qkv"].data_ptr(),
-                                      pool.kpools[li].data_ptr(),
-                                      pool.vpools[li].data_ptr(),
-                                      cb["att"].data_ptr(),
-                                      pool.table.data_ptr(),
-                                      self.pos.data_ptr(), B, self.heads,
-                                      K, pool.max_pages, scale, stream=s,
-                                      sync=False, D=self.hd)
-        else:
-            ops.kv_append_chunk(cb["qkv"].data_ptr(),
-                                lay["kcache"].data_ptr(),
-                                lay["vcache"].data_ptr(),
-                                self.pos.data_ptr(), B, self.heads, K,
-                                self.smax, stream=s, sync=False, D=self.hd)
-            ops.chunk_attention(cb["qkv"].data_ptr(),
-                                lay["kcache"].data_ptr(),
-                                lay["vcache"].data_ptr(),
-                                cb["att"].data_ptr(), self.pos.data_ptr(),
-                                B, self.heads, K, self.smax, scale,
-                                stream=s, sync=False, D=self.hd)
-
     def _enqueue_chunk(self, cb: Dict, B: int, K: int) -> None:
         """Record one chunked-verification pass's kernels on the session
         stream (no syncs — capturable). All position dependence reads the
@@ -764,11 +706,10 @@ class DecodeSession:
         M = B * K
         Hd, inter = self.hidden, self.inter
         ops, s = self._C.ops, self.stream
-        scale = 1.0 / float(np.sqrt(float(self.hd)))
-        ops.chunk_embed(cb["ids"].data_ptr(), self.tok.data_ptr(),
-                        self.posemb.data_ptr(), cb["h"].data_ptr(),
-                        self.pos.data_ptr(), B, K, self.smax, Hd, stream=s,
-                        sync=False)
+        ops.decode_embed(cb["ids"].data_ptr(), self.tok.data_ptr(),
+                         self.posemb.data_ptr(), cb["h"].data_ptr(),
+                         self.pos.data_ptr(), B, K, self.smax, Hd, stream=s,
+                         sync=False)
         if self.arch == "llama":
             ops.rmsnorm(0, cb["h"].data_ptr(),
                         self.layers[0]["rms1_g"].data_ptr(),
@@ -781,7 +722,8 @@ class DecodeSession:
                 ops.rope(0, cb["qkv"].data_ptr(), pos=self.pos.data_ptr(),
                          M=M, S=self.smax, H=self.heads, D=self.hd,
                          theta=self.theta, stream=s, sync=False, chunk=K)
-                self._kv_attn_chunk(li, lay, cb, B, K)
+                self._kv(li, lay, cb["qkv"].data_ptr(), K,
+                         cb["att"].data_ptr())
                 ops.gemm_bt(0, cb["att"].data_ptr(),
                             lay["proj_w"].data_ptr(), cb["x2"].data_ptr(),
                             M=M, N=Hd, K=Hd, epi=self._epi_none, stream=s,
@@ -822,7 +764,8 @@ class DecodeSession:
                             bias=lay["qkv_b"].data_ptr(),
                             M=M, N=3 * Hd, K=Hd, epi=self._epi_bias,
                             stream=s, sync=False)
-                self._kv_attn_chunk(li, lay, cb, B, K)
+                self._kv(li, lay, cb["qkv"].data_ptr(), K,
+                         cb["att"].data_ptr())
                 ops.gemm_bt(0, cb["att"].data_ptr(),
                             lay["proj_w"].data_ptr(), cb["x2"].data_ptr(),
                             bias=lay["proj_b"].data_ptr(),
