@@ -19,6 +19,41 @@ namespace {
 
 hipStream_t as_stream(uintptr_t s) { return (hipStream_t)s; }
 
+// The MX formats share their op signatures; one binding per op kind.
+// out_dtype 2 = raw fp32 C, 0 = fp16 through epilogue `epi`.
+using MxGemmFn = void (*)(const void*, const void*, const void*, const void*,
+                          void*, int, int, int, hipStream_t, int, int,
+                          const float*, const float*);
+void def_gemm_mx(py::module_& ops, const char* name, MxGemmFn fn) {
+  ops.def(name,
+          [fn](uintptr_t A, uintptr_t B, uintptr_t Sa, uintptr_t Sb,
+               uintptr_t C, int M, int N, int K, uintptr_t stream, bool sync,
+               int out_dtype, int epi, uintptr_t scale, uintptr_t bias) {
+            fn((void*)A, (void*)B, (void*)Sa, (void*)Sb, (void*)C, M, N, K,
+               as_stream(stream), out_dtype, epi, (const float*)scale,
+               (const float*)bias);
+            if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
+          },
+          py::arg("A"), py::arg("B"), py::arg("Sa"), py::arg("Sb"),
+          py::arg("C"), py::arg("M"), py::arg("N"), py::arg("K"),
+          py::arg("stream") = 0, py::arg("sync") = true,
+          py::arg("out_dtype") = 2, py::arg("epi") = 0, py::arg("scale") = 0,
+          py::arg("bias") = 0);
+}
+
+using MxQuantFn = void (*)(const void*, void*, void*, int64_t, int64_t,
+                           hipStream_t);
+void def_quantize_mx(py::module_& ops, const char* name, MxQuantFn fn) {
+  ops.def(name,
+          [fn](uintptr_t x, uintptr_t codes, uintptr_t scales, int64_t m,
+               int64_t k, uintptr_t stream, bool sync) {
+            fn((void*)x, (void*)codes, (void*)scales, m, k, as_stream(stream));
+            if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
+          },
+          py::arg("x"), py::arg("codes"), py::arg("scales"), py::arg("m"),
+          py::arg("k"), py::arg("stream") = 0, py::arg("sync") = true);
+}
+
 OpDesc op_from_dict(const py::dict& d) {
   OpDesc o;
   auto gi = [&](const char* k, int def) -> int {
@@ -617,25 +652,10 @@ PYBIND11_MODULE(_C, m) {
     launch_mx_frag_dump((void*)A, (void*)out, K, 0);
     TRT_HIP_CHECK(hipStreamSynchronize(0));
   });
-  ops.def("quantize_mxfp4",
-          [](uintptr_t x, uintptr_t codes, uintptr_t scales, int64_t m,
-             int64_t k, uintptr_t stream, bool sync) {
-            launch_quantize_mxfp4((void*)x, (void*)codes, (void*)scales, m, k,
-                                  as_stream(stream));
-            if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
-          },
-          py::arg("x"), py::arg("codes"), py::arg("scales"), py::arg("m"),
-          py::arg("k"), py::arg("stream") = 0, py::arg("sync") = true);
-  ops.def("gemm_mxfp4",
-          [](uintptr_t A, uintptr_t B, uintptr_t Sa, uintptr_t Sb,
-             uintptr_t C, int M, int N, int K, uintptr_t stream, bool sync) {
-            launch_gemm_mxfp4((void*)A, (void*)B, (void*)Sa, (void*)Sb,
-                              (void*)C, M, N, K, as_stream(stream));
-            if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
-          },
-          py::arg("A"), py::arg("B"), py::arg("Sa"), py::arg("Sb"),
-          py::arg("C"), py::arg("M"), py::arg("N"), py::arg("K"),
-          py::arg("stream") = 0, py::arg("sync") = true);
+  def_quantize_mx(ops, "quantize_mxfp4", launch_quantize_mxfp4);
+  def_quantize_mx(ops, "quantize_mxfp8", launch_quantize_mxfp8);
+  def_gemm_mx(ops, "gemm_mxfp4", launch_gemm_mxfp4);
+  def_gemm_mx(ops, "gemm_mxfp8", launch_gemm_mxfp8);
   ops.def("mx4_probe",
           [](uintptr_t A, uintptr_t B, uintptr_t Sa, uintptr_t Sb,
              uintptr_t D) {
@@ -643,16 +663,6 @@ PYBIND11_MODULE(_C, m) {
                              (void*)D, 0);
             TRT_HIP_CHECK(hipStreamSynchronize(0));
           });
-  ops.def("gemm_mxfp8",
-          [](uintptr_t A, uintptr_t B, uintptr_t Sa, uintptr_t Sb,
-             uintptr_t C, int M, int N, int K, uintptr_t stream, bool sync) {
-            launch_gemm_mxfp8((void*)A, (void*)B, (void*)Sa, (void*)Sb,
-                              (void*)C, M, N, K, as_stream(stream));
-            if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
-          },
-          py::arg("A"), py::arg("B"), py::arg("Sa"), py::arg("Sb"),
-          py::arg("C"), py::arg("M"), py::arg("N"), py::arg("K"),
-          py::arg("stream") = 0, py::arg("sync") = true);
   ops.def("kv_append",
           [](uintptr_t qkv, uintptr_t kc, uintptr_t vc, int B, int H,
              int rows, int smax, uintptr_t pos, uintptr_t table,

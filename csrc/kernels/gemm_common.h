@@ -364,43 +364,13 @@ __device__ __forceinline__ void store_epilogue(
 // later tiles' loads in flight across the barrier.)
 template <int G>
 __device__ __forceinline__ void wait_tiles_inflight(int ahead) {
-  if (ahead >= 2) {
-    if constexpr (G == 2)
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (G == 3)
-      asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (G == 4)
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (G == 6)
-      asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if constexpr (G == 9)
-      asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
-    else if constexpr (G == 10)
-      asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-    else if constexpr (G == 12)
-      asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-  } else if (ahead == 1) {
-    if constexpr (G == 2)
-      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if constexpr (G == 3)
-      asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (G == 4)
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (G == 6)
-      asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (G == 9)
-      asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-    else if constexpr (G == 10)
-      asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    else if constexpr (G == 12)
-      asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  } else {
+  static_assert(2 * G <= 63, "vmcnt is a 6-bit counter");
+  if (ahead >= 2)
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * G) : "memory");
+  else if (ahead == 1)
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G) : "memory");
+  else
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
 }
 
 // Pick the pipeline depth: grid-starved shapes (fewer blocks than ~1.5x

@@ -111,9 +111,11 @@ void launch_attention(int dtype, const void* qkv, void* out, int B, int S,
 void launch_seqlens(const void* ids, void* lens, int B, int S, int pad_id,
                     hipStream_t stream);
 
-// MXFP8 (OCP MX: fp8-e4m3 elements + e8m0 per-32-block scales) GEMM on
-// the CDNA4 scaled MFMA 16x16x128. B transposed [N][K]; scales u8
-// [M][K/32] / [N][K/32]; C fp32.
+// OCP MX (fp8-e4m3 or fp4-e2m1 elements + e8m0 per-32-block scales) GEMMs
+// on the CDNA4 scaled MFMA 16x16x128 and their row quantizers. B transposed
+// [N][K]; scales u8 [M][K/32] / [N][K/32]; fp4 codes packed two per byte.
+// out_dtype 2: C is the raw fp32 product; 0: C is fp16 through epilogue
+// `epi` with per-column scale / bias. K % 128 == 0 (fp8), % 256 (fp4).
 void launch_mx_frag_dump(const void* A, void* out, int K, hipStream_t s);
 void launch_quantize_mxfp4(const void* x, void* codes, void* scales,
                            int64_t m, int64_t k, hipStream_t stream);

@@ -8,6 +8,7 @@
 #include <hip/hip_fp8.h>
 
 #include "../common.h"
+#include "mx_common.h"
 
 namespace trtlab {
 
@@ -88,9 +89,9 @@ __device__ __forceinline__ void store8_fp8(unsigned char* p,
 
 // Producer-fused OCP MX quantization of one normalized 8-elem chunk:
 // the 32-element MX block spans the QUAD of adjacent lanes owning chunks
-// 4q..4q+3, so the block amax is a 2-step shfl_xor quad-reduce. Code
-// packing and e8m0 scale bias match quantize_mxfp4/8_kernel exactly
-// (gemm_mx.hip) so the scaled-MFMA GEMMs consume either producer.
+// 4q..4q+3, so the block amax is a 2-step shfl_xor quad-reduce. Exponent
+// and element encoders are the row quantizers' own (mx_common.h), so the
+// scaled-MFMA GEMMs consume either producer.
 __device__ __forceinline__ void store8_mx(
     unsigned char* __restrict__ codes, unsigned char* __restrict__ scales,
     int chunk, const float* v8, int mx_mode /*4 or 8*/, int lane) {
@@ -99,43 +100,20 @@ __device__ __forceinline__ void store8_mx(
   for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v8[j]));
   amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
   amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
-  int bias = (mx_mode == 4) ? 2 : 8;  // e2m1 emax 2, e4m3 emax 8
-  int e = (amax > 0.f) ? (int)floorf(log2f(amax)) - bias : 0;
-  e = e < -127 ? -127 : (e > 127 ? 127 : e);
+  int e = mx_block_exponent(amax, (mx_mode == 4) ? 2 : 8);
   if ((lane & 3) == 0) scales[chunk >> 2] = (unsigned char)(e + 127);
   float inv = exp2f((float)-e);
   if (mx_mode == 8) {
     unsigned char out[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      __hip_fp8_e4m3 q = __hip_fp8_e4m3(
-          fminf(fmaxf(v8[j] * inv, -448.f), 448.f));
-      out[j] = *(const unsigned char*)&q;
-    }
+    for (int j = 0; j < 8; ++j) out[j] = mx_encode_e4m3(v8[j] * inv);
     *(float2v*)(codes + chunk * 8) = *(const float2v*)out;
   } else {
     unsigned char out[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      unsigned char byte = 0;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        float q = v8[2 * j + h] * inv;
-        float a = fabsf(q);
-        int m;
-        if (a < 0.25f) m = 0;
-        else if (a < 0.75f) m = 1;
-        else if (a < 1.25f) m = 2;
-        else if (a < 1.75f) m = 3;
-        else if (a < 2.5f) m = 4;
-        else if (a < 3.5f) m = 5;
-        else if (a < 5.0f) m = 6;
-        else m = 7;
-        unsigned char code = (unsigned char)(q < 0.f ? (m | 8) : m);
-        byte |= (unsigned char)(code << (4 * h));
-      }
-      out[j] = byte;
-    }
+    for (int j = 0; j < 4; ++j)  // low nibble = even element
+      out[j] = (unsigned char)(mx_encode_e2m1(v8[2 * j] * inv) |
+                               (mx_encode_e2m1(v8[2 * j + 1] * inv) << 4));
     *(float*)(codes + chunk * 4) = *(const float*)out;
   }
 }

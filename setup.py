@@ -36,6 +36,7 @@ SOURCES = [
 HEADERS = [
     "csrc/common.h",
     "csrc/kernels/gemm_common.h",
+    "csrc/kernels/mx_common.h",
     "csrc/kernels/launchers.h",
     "csrc/runtime/runtime.h",
     "csrc/runtime/comm.h",

@@ -3,9 +3,9 @@
 MXFP8: fp8-e4m3 elements with one shared e8m0 scale per 32-element block
 (along K). The GPU side is csrc/kernels/gemm_mx.hip on the CDNA4 scaled
 MFMA (mfma_scale_f32_16x16x128_f8f6f4) — gfx950's highest-throughput GEMM
-instruction, with no equivalent in the CUDA reference. Engine-level MX
-plans are round-2 work; this module + the raw op are the validated
-foundation (tests/test_kernels_gpu.py, tools/bench_mx.py).
+instruction, with no equivalent in the CUDA reference. The planner's
+DT_MX8 / DT_MX4 plans quantize weights with these codecs; activations are
+quantized on the device (tests/test_mx_kernels_gpu.py, tools/bench_mx.py).
 """
 from __future__ import annotations
 
