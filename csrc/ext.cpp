@@ -85,6 +85,7 @@ OpDesc op_from_dict(const py::dict& d) {
   o.eps = gf("eps", 1e-5f);
   o.n_elems = gl("n_elems", 0);
   o.B = gi("B", 0); o.S = gi("S", 0); o.NH = gi("NH", 0); o.HD = gi("HD", 0);
+  o.NKV = gi("NKV", 0);
   o.att_scale = gf("att_scale", 1.0f);
   o.causal = gi("causal", 0);
   o.res_scale = gf("res_scale", 1.0f);
@@ -529,16 +530,17 @@ PYBIND11_MODULE(_C, m) {
           py::arg("n"), py::arg("stream") = 0, py::arg("sync") = true);
   ops.def("rope",
           [](int dtype, uintptr_t qkv, uintptr_t pos, int M, int S, int H,
-             int D, float theta, uintptr_t stream, bool sync, int chunk) {
+             int D, float theta, uintptr_t stream, bool sync, int chunk,
+             int kv_heads) {
             launch_rope(dtype, (void*)qkv, (void*)pos, M, S, H, D, theta,
-                        as_stream(stream), chunk);
+                        as_stream(stream), chunk, kv_heads);
             if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
           },
           py::arg("dtype"), py::arg("qkv"), py::arg("pos") = 0,
           py::arg("M") = 0, py::arg("S") = 0, py::arg("H") = 0,
           py::arg("D") = 0, py::arg("theta") = 10000.0f,
           py::arg("stream") = 0, py::arg("sync") = true,
-          py::arg("chunk") = 0);
+          py::arg("chunk") = 0, py::arg("kv_heads") = 0);
   ops.def("argmax_rows",
           [](uintptr_t x, uintptr_t out, int M, int V, uintptr_t stream,
              bool sync) {
@@ -666,32 +668,35 @@ PYBIND11_MODULE(_C, m) {
   ops.def("kv_append",
           [](uintptr_t qkv, uintptr_t kc, uintptr_t vc, int B, int H,
              int rows, int smax, uintptr_t pos, uintptr_t table,
-             int max_pages, uintptr_t stream, bool sync, int D) {
+             int max_pages, uintptr_t stream, bool sync, int D,
+             int kv_heads) {
             launch_kv_append((void*)qkv, (void*)kc, (void*)vc, (void*)pos,
                              (void*)table, max_pages, B, H, rows, smax,
-                             as_stream(stream), D);
+                             as_stream(stream), D, kv_heads);
             if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
           },
           py::arg("qkv"), py::arg("kcache"), py::arg("vcache"), py::arg("B"),
           py::arg("H"), py::arg("rows"), py::arg("smax"), py::arg("pos") = 0,
           py::arg("table") = 0, py::arg("max_pages") = 0,
-          py::arg("stream") = 0, py::arg("sync") = true, py::arg("D") = 64);
+          py::arg("stream") = 0, py::arg("sync") = true, py::arg("D") = 64,
+          py::arg("kv_heads") = 0);
   ops.def("decode_attention",
           [](uintptr_t qkv, uintptr_t kc, uintptr_t vc, uintptr_t out,
              uintptr_t pos, int B, int H, int rows, int smax, float scale,
              uintptr_t table, int max_pages, uintptr_t stream, bool sync,
-             int D) {
+             int D, int kv_heads) {
             launch_decode_attention((void*)qkv, (void*)kc, (void*)vc,
                                     (void*)out, (void*)pos, (void*)table,
                                     max_pages, B, H, rows, smax, scale,
-                                    as_stream(stream), D);
+                                    as_stream(stream), D, kv_heads);
             if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
           },
           py::arg("qkv"), py::arg("kcache"), py::arg("vcache"),
           py::arg("out"), py::arg("pos"), py::arg("B"), py::arg("H"),
           py::arg("rows"), py::arg("smax"), py::arg("scale"),
           py::arg("table") = 0, py::arg("max_pages") = 0,
-          py::arg("stream") = 0, py::arg("sync") = true, py::arg("D") = 64);
+          py::arg("stream") = 0, py::arg("sync") = true, py::arg("D") = 64,
+          py::arg("kv_heads") = 0);
   ops.def("decode_embed",
           [](uintptr_t ids, uintptr_t tok, uintptr_t pe, uintptr_t out,
              uintptr_t pos, int B, int rows, int smax, int hidden,
@@ -737,16 +742,17 @@ PYBIND11_MODULE(_C, m) {
   ops.def("attention",
           [](int dtype, uintptr_t qkv, uintptr_t out, int B, int S, int H,
              int D, float scale, uintptr_t stream, bool sync, int causal,
-             uintptr_t seqlens) {
+             uintptr_t seqlens, int kv_heads) {
             launch_attention(dtype, (void*)qkv, (void*)out, B, S, H, D, scale,
                              as_stream(stream), -1, 1.0f, (void*)seqlens,
-                             causal);
+                             causal, kv_heads);
             if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
           },
           py::arg("dtype"), py::arg("qkv"), py::arg("out"), py::arg("B"),
           py::arg("S"), py::arg("H"), py::arg("D"), py::arg("scale"),
           py::arg("stream") = 0, py::arg("sync") = true,
-          py::arg("causal") = 0, py::arg("seqlens") = 0);
+          py::arg("causal") = 0, py::arg("seqlens") = 0,
+          py::arg("kv_heads") = 0);
 
   // --------------------------------------------------------------- comm
   // Owned RCCL collective layer (no torch.distributed in the data path).

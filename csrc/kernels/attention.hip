@@ -3,6 +3,9 @@
 //
 // Input: qkv [B*S, 3*H*D] (the fused QKV projection output, column blocks
 // q|k|v, each H*D with head-major (h,d) minor d). Output: [B*S, H*D].
+// Grouped-query: the k and v blocks hold Hkv <= H heads (row width
+// (H + 2*Hkv)*D) and query head h reads kv head h / (H / Hkv); only these
+// addresses differ from MHA (Hkv = H).
 //
 // One workgroup per (b, h, 64-query-row block); 4 waves own 16 query rows
 // each. Keys/values stream through LDS in 128-key tiles with an ONLINE
@@ -35,7 +38,7 @@ template <typename T, typename OT = T>
 __global__ __launch_bounds__(256) void attention_kernel(
     const T* __restrict__ qkv, OT* __restrict__ out, int B, int S, int H,
     int D, float scale, float out_scale, const int* __restrict__ seqlens,
-    int causal) {
+    int causal, int Hkv) {
   // LDS: Q [64][64] | K [128][64] | Vt 2x[64][64] | P 4 waves x 2x[16][64]
   __shared__ __attribute__((aligned(16))) char smem[8192 + 16384 * 2 + 16384];
   char* Qs = smem;                  // 8 KiB
@@ -53,12 +56,13 @@ __global__ __launch_bounds__(256) void attention_kernel(
   const int b = bh / H;
   const int h = bh % H;
   const int hid = H * D;
-  const int row_stride = 3 * hid;
+  const int row_stride = (H + 2 * Hkv) * D;
+  const int hk = h / (H / Hkv);  // kv head of this query head
 
   const T* base = qkv + (int64_t)b * S * row_stride;
   const int qoff = h * D;
-  const int koff = hid + h * D;
-  const int voff = 2 * hid + h * D;
+  const int koff = hid + hk * D;
+  const int voff = hid + (Hkv + hk) * D;
 
   auto swz = [](uint32_t row, uint32_t colbyte) {
     return row * 128 + (colbyte ^ ((row & 7) << 4));
@@ -275,7 +279,7 @@ template <typename T, typename OT = T>
 __global__ __launch_bounds__(256) void attention_kernel_d128(
     const T* __restrict__ qkv, OT* __restrict__ out, int B, int S, int H,
     float scale, float out_scale, const int* __restrict__ seqlens,
-    int causal) {
+    int causal, int Hkv) {
   constexpr int D = 128;
   __shared__ __attribute__((aligned(16))) char smem[16384 * 3 + 8192];
   char* Qs = smem;                   // [64 q][128 d], 256-B rows
@@ -293,12 +297,13 @@ __global__ __launch_bounds__(256) void attention_kernel_d128(
   const int b = bh / H;
   const int h = bh % H;
   const int hid = H * D;
-  const int row_stride = 3 * hid;
+  const int row_stride = (H + 2 * Hkv) * D;
+  const int hk = h / (H / Hkv);  // kv head of this query head
 
   const T* base = qkv + (int64_t)b * S * row_stride;
   const int qoff = h * D;
-  const int koff = hid + h * D;
-  const int voff = 2 * hid + h * D;
+  const int koff = hid + hk * D;
+  const int voff = hid + (Hkv + hk) * D;
 
   // 256-B-row swizzle: 16 distinct 16-B offsets per 16 rows (bank period
   // = 256 B on 64x4-B LDS banks) -> conflict-free frag reads and writes
@@ -507,9 +512,13 @@ void launch_attention_probe(int* dbg, int B, int S, int H, int D,
 void launch_attention(int dtype, const void* qkv, void* out, int B, int S,
                       int H, int D, float scale, hipStream_t stream,
                       int out_dtype, float out_scale, const void* seqlens,
-                      int causal) {
+                      int causal, int kv_heads) {
   if (D != 64 && D != 128)
     throw std::runtime_error("attention: head_dim must be 64 or 128");
+  int Hkv = kv_heads > 0 ? kv_heads : H;
+  if (Hkv > H || H % Hkv != 0)
+    throw std::runtime_error(
+        "attention: heads must be a multiple of kv_heads");
   if (S < 1) throw std::runtime_error("attention: S must be >= 1");
   dim3 grid(B * H * ((S + 63) / 64));  // 64-query-row blocks (+ tail)
   dim3 block(256);
@@ -520,16 +529,16 @@ void launch_attention(int dtype, const void* qkv, void* out, int B, int S,
         hipLaunchKernelGGL((attention_kernel_d128<_Float16, __hip_fp8_e4m3>),
                            grid, block, 0, stream, (const _Float16*)qkv,
                            (__hip_fp8_e4m3*)out, B, S, H, scale, out_scale,
-                           lens, causal);
+                           lens, causal, Hkv);
       else
         hipLaunchKernelGGL((attention_kernel_d128<_Float16, _Float16>), grid,
                            block, 0, stream, (const _Float16*)qkv,
                            (_Float16*)out, B, S, H, scale, out_scale, lens,
-                           causal);
+                           causal, Hkv);
     } else {
       hipLaunchKernelGGL((attention_kernel_d128<__bf16, __bf16>), grid, block,
                          0, stream, (const __bf16*)qkv, (__bf16*)out, B, S, H,
-                         scale, out_scale, lens, causal);
+                         scale, out_scale, lens, causal, Hkv);
     }
     return;
   }
@@ -538,15 +547,15 @@ void launch_attention(int dtype, const void* qkv, void* out, int B, int S,
       hipLaunchKernelGGL((attention_kernel<_Float16, __hip_fp8_e4m3>), grid,
                          block, 0, stream, (const _Float16*)qkv,
                          (__hip_fp8_e4m3*)out, B, S, H, D, scale, out_scale,
-                         lens, causal);
+                         lens, causal, Hkv);
     else
       hipLaunchKernelGGL((attention_kernel<_Float16, _Float16>), grid, block,
                          0, stream, (const _Float16*)qkv, (_Float16*)out, B,
-                         S, H, D, scale, out_scale, lens, causal);
+                         S, H, D, scale, out_scale, lens, causal, Hkv);
   } else {
     hipLaunchKernelGGL((attention_kernel<__bf16, __bf16>), grid, block, 0,
                        stream, (const __bf16*)qkv, (__bf16*)out, B, S, H, D,
-                       scale, out_scale, lens, causal);
+                       scale, out_scale, lens, causal, Hkv);
   }
 }
 

@@ -18,6 +18,11 @@
 //          null: base position 0).
 //   KV   — cache layout policy (DenseKV / PagedKV below), the only code
 //          that knows how row t of (slot, head) is addressed.
+// Grouped-query attention (Hq query heads over Hkv kv heads, G = Hq/Hkv)
+// is not a third axis of the layouts: the caches simply hold Hkv heads
+// (the policies are addressed with H := Hkv), the fused qkv row narrows to
+// [q: Hq*D | k: Hkv*D | v: Hkv*D], and the attention workgroup grows to G
+// waves (see decode_attention_kernel). Hkv = Hq is plain MHA, G = 1.
 //
 // Bounds rule (every kernel here, both layouts):
 //   * pos[b] < 0 marks slot b IDLE: the block exits — no cache write, no
@@ -67,13 +72,13 @@ struct PagedKV {
 };
 
 // Scatter K/V head rows from the fused qkv projection output (qkv
-// [B*rows, 3*H*D]) into the cache at position (pos ? pos[b] : 0) + q.
-// One block per (b, h, q).
+// [B*rows, (Hq + 2*Hkv)*D]) into the cache at position
+// (pos ? pos[b] : 0) + q. One block per (b, kv head, q); H is Hkv.
 template <class KV>
 __global__ __launch_bounds__(64) void kv_append_kernel(
     const _Float16* __restrict__ qkv, _Float16* __restrict__ kcache,
     _Float16* __restrict__ vcache, const int* __restrict__ pos, KV kv, int H,
-    int rows, int smax, int D) {
+    int Hq, int rows, int smax, int D) {
   int q = blockIdx.x % rows;
   int bh = blockIdx.x / rows;
   int b = bh / H, h = bh % H;
@@ -86,24 +91,34 @@ __global__ __launch_bounds__(64) void kv_append_kernel(
   if (p >= smax) p = smax - 1;
   int64_t dst = kv.row(b, h, H, D, p);
   if (dst < 0) return;  // unmapped page (host error) — fail soft, not wild
-  int hid = H * D;
-  int64_t src = ((int64_t)b * rows + q) * 3 * hid + h * D;
+  int khid = H * D;
+  int64_t src = ((int64_t)b * rows + q) * (Hq + 2 * H) * D + Hq * D + h * D;
   for (int d = threadIdx.x; d < D; d += 64) {
-    kcache[dst + d] = qkv[src + hid + d];
-    vcache[dst + d] = qkv[src + 2 * hid + d];
+    kcache[dst + d] = qkv[src + d];
+    vcache[dst + d] = qkv[src + khid + d];
   }
+}
+
+// Hq query heads over Hkv kv heads: kv_heads = 0 means Hkv = Hq (MHA).
+static int gqa_kv_heads(const char* op, int H, int kv_heads) {
+  int Hkv = kv_heads > 0 ? kv_heads : H;
+  if (Hkv > H || H % Hkv != 0)
+    throw std::runtime_error(std::string(op) +
+                             ": heads must be a multiple of kv_heads");
+  return Hkv;
 }
 
 void launch_kv_append(const void* qkv, void* kcache, void* vcache,
                       const void* pos, const void* table, int max_pages,
                       int B, int H, int rows, int smax, hipStream_t stream,
-                      int D) {
+                      int D, int kv_heads) {
   if (rows < 1) throw std::runtime_error("kv_append: rows < 1");
+  int Hkv = gqa_kv_heads("kv_append", H, kv_heads);
   auto L = [&](auto kv) {
-    hipLaunchKernelGGL(kv_append_kernel<decltype(kv)>, dim3(B * H * rows),
+    hipLaunchKernelGGL(kv_append_kernel<decltype(kv)>, dim3(B * Hkv * rows),
                        dim3(64), 0, stream, (const _Float16*)qkv,
                        (_Float16*)kcache, (_Float16*)vcache, (const int*)pos,
-                       kv, H, rows, smax, D);
+                       kv, Hkv, H, rows, smax, D);
   };
   if (table) L(PagedKV{(const int*)table, max_pages});
   else L(DenseKV{smax});
@@ -116,18 +131,33 @@ void launch_kv_append(const void* qkv, void* kcache, void* vcache,
 // owns keys lane, lane+64, ... for the score pass (its K rows are whole
 // cachelines), then output element d = lane (+64) for the PV pass with
 // the probabilities broadcast through LDS.
-template <int D, class KV>  // head_dim 64 or 128
-__global__ __launch_bounds__(64) void decode_attention_kernel(
+//
+// Grouped-query: one workgroup per (b, kv head, q) with G waves; wave g
+// is query head hk*G + g and runs the per-wave body above against the kv
+// head's rows with its own 4096-float slice of p_s. The G waves share a
+// CU and walk the same K/V rows in step, so a row leaves HBM once per
+// group (the other G-1 reads hit the CU's L1/L2) instead of once per
+// query head. The __syncthreads() are workgroup-wide; idle exit and n
+// depend on (b, q) only, so every wave of a group takes them alike.
+// G = 1 is the MHA kernel: same grid, same 16 KiB of LDS, same
+// arithmetic order. p_s is G * 16 KiB of static LDS (128 KiB at G = 8,
+// within the 160 KiB a gfx950 workgroup may declare).
+template <int D, int G, class KV>  // head_dim 64 or 128; group 1,2,4,8
+__global__ __launch_bounds__(64 * G) void decode_attention_kernel(
     const _Float16* __restrict__ qkv, const _Float16* __restrict__ kcache,
     const _Float16* __restrict__ vcache, _Float16* __restrict__ out,
     const int* __restrict__ pos, KV kv, int H, int rows, int smax,
     float scale) {
-  __shared__ float p_s[4096];
+  __shared__ float p_all[G * 4096];
   int q = blockIdx.x % rows;
   int bh = blockIdx.x / rows;
-  int b = bh / H, h = bh % H;
-  int lane = threadIdx.x;
-  int hid = H * D;
+  int b = bh / H, hk = bh % H;  // H = kv heads
+  int lane = threadIdx.x & 63;
+  // wave index, kept scalar so the K/V row addresses stay wave-uniform
+  int g = G == 1 ? 0 : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  float* p_s = p_all + g * 4096;
+  int h = hk * G + g;           // query head
+  int hid = H * G * D;          // q block / output row width
   int p0 = pos[b];
   if (p0 < 0) return;  // idle slot: stale output row unused
   int n = p0 + q + 1;
@@ -136,7 +166,8 @@ __global__ __launch_bounds__(64) void decode_attention_kernel(
   // q for this head (fp16 registers: D=128 stays within budget)
   _Float16 qv[D];
   {
-    const _Float16* qrow = qkv + ((int64_t)b * rows + q) * 3 * hid + h * D;
+    const _Float16* qrow =
+        qkv + ((int64_t)b * rows + q) * (G + 2) * H * D + h * D;
 #pragma unroll
     for (int c = 0; c < D / 8; ++c)
       *(half8v*)(qv + c * 8) = *(const half8v*)(qrow + c * 8);
@@ -145,7 +176,7 @@ __global__ __launch_bounds__(64) void decode_attention_kernel(
   // scores for this lane's keys
   float m = -3.0e38f;
   for (int t = lane; t < n; t += 64) {
-    const _Float16* krow = kcache + kv.row(b, h, H, D, t);
+    const _Float16* krow = kcache + kv.row(b, hk, H, D, t);
     float s = 0.f;
 #pragma unroll
     for (int c = 0; c < D / 8; ++c) {
@@ -176,7 +207,7 @@ __global__ __launch_bounds__(64) void decode_attention_kernel(
 #pragma unroll
   for (int j = 0; j < D / 64; ++j) acc[j] = 0.f;
   for (int t = 0; t < n; ++t) {
-    const _Float16* vrow = vcache + kv.row(b, h, H, D, t);
+    const _Float16* vrow = vcache + kv.row(b, hk, H, D, t);
     float p = p_s[t];
 #pragma unroll
     for (int j = 0; j < D / 64; ++j)
@@ -192,27 +223,40 @@ void launch_decode_attention(const void* qkv, const void* kcache,
                              const void* vcache, void* out, const void* pos,
                              const void* table, int max_pages, int B, int H,
                              int rows, int smax, float scale,
-                             hipStream_t stream, int D) {
+                             hipStream_t stream, int D, int kv_heads) {
   if (smax > 4096)
     throw std::runtime_error("decode_attention: smax > 4096 unsupported");
   if (D != 64 && D != 128)
     throw std::runtime_error("decode_attention: head_dim must be 64 or 128");
   if (rows < 1) throw std::runtime_error("decode_attention: rows < 1");
-  auto L = [&](auto d_c, auto kv) {
+  int Hkv = gqa_kv_heads("decode_attention", H, kv_heads);
+  int G = H / Hkv;
+  if (G != 1 && G != 2 && G != 4 && G != 8)
+    throw std::runtime_error(
+        "decode_attention: heads / kv_heads must be 1, 2, 4 or 8");
+  auto L = [&](auto d_c, auto g_c, auto kv) {
     hipLaunchKernelGGL(
-        (decode_attention_kernel<decltype(d_c)::value, decltype(kv)>),
-        dim3(B * H * rows), dim3(64), 0, stream, (const _Float16*)qkv,
-        (const _Float16*)kcache, (const _Float16*)vcache, (_Float16*)out,
-        (const int*)pos, kv, H, rows, smax, scale);
+        (decode_attention_kernel<decltype(d_c)::value, decltype(g_c)::value,
+                                 decltype(kv)>),
+        dim3(B * Hkv * rows), dim3(64 * decltype(g_c)::value), 0, stream,
+        (const _Float16*)qkv, (const _Float16*)kcache,
+        (const _Float16*)vcache, (_Float16*)out, (const int*)pos, kv, Hkv,
+        rows, smax, scale);
+  };
+  auto LG = [&](auto d_c, auto kv) {
+    if (G == 1) L(d_c, std::integral_constant<int, 1>{}, kv);
+    else if (G == 2) L(d_c, std::integral_constant<int, 2>{}, kv);
+    else if (G == 4) L(d_c, std::integral_constant<int, 4>{}, kv);
+    else L(d_c, std::integral_constant<int, 8>{}, kv);
   };
   using D64 = std::integral_constant<int, 64>;
   using D128 = std::integral_constant<int, 128>;
   PagedKV paged{(const int*)table, max_pages};
   DenseKV dense{smax};
-  if (table && D == 128) L(D128{}, paged);
-  else if (table) L(D64{}, paged);
-  else if (D == 128) L(D128{}, dense);
-  else L(D64{}, dense);
+  if (table && D == 128) LG(D128{}, paged);
+  else if (table) LG(D64{}, paged);
+  else if (D == 128) LG(D128{}, dense);
+  else LG(D64{}, dense);
 }
 
 // Token + position embedding: out[b*rows + q] = tok[ids[b*rows + q]] +

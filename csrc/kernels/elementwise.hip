@@ -445,22 +445,24 @@ void launch_silu_mul(int dtype, const void* a, const void* b, void* out,
 
 // ---- rotary position embedding (RoPE, LLaMA-style interleaved-half) ----
 // In-place on the q and k column blocks of the fused qkv rows
-// [M = B*S, 3*H*D]: for head h, pair (d, d + D/2), angle =
-// pos * theta^(-2d/D). Row positions: pos = row % S (full-sequence
-// forward; decode uses per-slot device pos via rope_pos).
+// [M = B*S, (H + 2*Hkv)*D] (Hkv = H: the MHA row [M, 3*H*D]): H query
+// heads then Hkv key heads rotate, v stays untouched; for head h, pair
+// (d, d + D/2), angle = pos * theta^(-2d/D). The k block follows the q
+// block directly, so head index hh in [0, H + Hkv) addresses both. Row
+// positions: pos = row % S (full-sequence forward; decode uses per-slot
+// device pos via rope_pos).
 template <typename T>
 __global__ void rope_kernel(T* __restrict__ qkv,
                             const int* __restrict__ pos_dev, int M, int S,
-                            int H, int D, float theta, int K /*B for dev*/) {
+                            int H, int Hkv, int D, float theta,
+                            int K /*B for dev*/) {
   int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int half = D / 2;
-  int64_t per_row = (int64_t)2 * H * half;  // q and k rotate, v untouched
+  int64_t per_row = (int64_t)(H + Hkv) * half;  // q and k rotate
   if (idx >= (int64_t)M * per_row) return;
   int64_t row = idx / per_row;
   int r = (int)(idx - row * per_row);
-  int qk = r / (H * half);        // 0 = q block, 1 = k block
-  int rr = r % (H * half);
-  int h = rr / half, d = rr % half;
+  int hh = r / half, d = r % half;  // hh < H: q head, else k head hh - H
   int p;
   if (!pos_dev)
     p = (int)(row % S);                       // full-sequence forward
@@ -470,8 +472,7 @@ __global__ void rope_kernel(T* __restrict__ qkv,
     p = pos_dev[row];                         // decode step: one row/slot
   if (p < 0 || (K > 0 && pos_dev[row / K] < 0))
     return;  // idle slot (decode)
-  int hid = H * D;
-  T* base = qkv + row * (int64_t)3 * hid + qk * hid + h * D;
+  T* base = qkv + row * (int64_t)(H + 2 * Hkv) * D + hh * D;
   float ang = (float)p * __powf(theta, -2.0f * (float)d / (float)D);
   float c, sn;
   __sincosf(ang, &sn, &c);
@@ -481,14 +482,18 @@ __global__ void rope_kernel(T* __restrict__ qkv,
 }
 
 void launch_rope(int dtype, void* qkv, const void* pos_dev, int M, int S,
-                 int H, int D, float theta, hipStream_t stream, int chunk) {
+                 int H, int D, float theta, hipStream_t stream, int chunk,
+                 int kv_heads) {
   if (D % 2 != 0) throw std::runtime_error("rope: D % 2 != 0");
-  int64_t total = (int64_t)M * 2 * H * (D / 2);
+  int Hkv = kv_heads > 0 ? kv_heads : H;
+  if (Hkv > H || H % Hkv != 0)
+    throw std::runtime_error("rope: heads must be a multiple of kv_heads");
+  int64_t total = (int64_t)M * (H + Hkv) * (D / 2);
   int blocks = (int)std::min<int64_t>((total + 255) / 256, 16384);
   if (dtype != 0) throw std::runtime_error("rope: fp16 only");
   hipLaunchKernelGGL((rope_kernel<_Float16>), dim3(blocks), dim3(256), 0,
-                     stream, (_Float16*)qkv, (const int*)pos_dev, M, S, H, D,
-                     theta, chunk);
+                     stream, (_Float16*)qkv, (const int*)pos_dev, M, S, H,
+                     Hkv, D, theta, chunk);
 }
 
 // ---- row-wise argmax: fp16 logits [M, V] -> int32 index [M] ----

@@ -64,7 +64,7 @@ void launch_silu_mul(int dtype, const void* a, const void* b, void* out,
 // row % K (speculative verify chunk, rows grouped K-per-slot).
 void launch_rope(int dtype, void* qkv, const void* pos_dev, int M, int S,
                  int H, int D, float theta, hipStream_t stream,
-                 int chunk = 0);
+                 int chunk = 0, int kv_heads = 0);
 // Fused ResNet bottleneck tail: conv3x3(s1,p1,Cm)+BN+ReLU feeding
 // conv1x1(Cm->Co)+BN+residual+ReLU in ONE kernel (intermediate stays in
 // LDS). Cm in {64,128}; fp16 only.
@@ -104,7 +104,8 @@ void launch_cast(int dtype, bool to_f32, const void* in, void* out, int64_t n,
 void launch_attention(int dtype, const void* qkv, void* out, int B, int S,
                       int H, int D, float scale, hipStream_t stream,
                       int out_dtype = -1, float out_scale = 1.0f,
-                      const void* seqlens = nullptr, int causal = 0);
+                      const void* seqlens = nullptr, int causal = 0,
+                      int kv_heads = 0);
 
 // lens[b] = count of non-pad tokens in right-padded ids (>=1); feeds the
 // variable-length attention mask.
@@ -144,12 +145,13 @@ void launch_quantize_mxfp8(const void* x, void* codes, void* scales,
 void launch_kv_append(const void* qkv, void* kcache, void* vcache,
                       const void* pos, const void* table, int max_pages,
                       int B, int H, int rows, int smax, hipStream_t stream,
-                      int D = 64);
+                      int D = 64, int kv_heads = 0);
 void launch_decode_attention(const void* qkv, const void* kcache,
                              const void* vcache, void* out, const void* pos,
                              const void* table, int max_pages, int B, int H,
                              int rows, int smax, float scale,
-                             hipStream_t stream, int D = 64);
+                             hipStream_t stream, int D = 64,
+                             int kv_heads = 0);
 void launch_decode_embed(const void* ids, const void* tok, const void* posemb,
                          void* out, const void* pos, int B, int rows,
                          int smax, int hidden, hipStream_t stream);

@@ -255,7 +255,8 @@ void ExecutionContext::enqueue_all(hipStream_t s) {
                          op.q_scale != 0.f && op.epi == 3
                              ? 1.0f / op.q_scale
                              : 1.0f,
-                         A(op.in2_off) /*seqlens or null*/, op.causal);
+                         A(op.in2_off) /*seqlens or null*/, op.causal,
+                         op.NKV);
         break;
       case kSeqLens:
         // op.epi carries pad_id
@@ -310,7 +311,7 @@ void ExecutionContext::enqueue_all(hipStream_t s) {
       case kRope:
         // in-place on the (arena-aliased) qkv buffer; eps carries theta
         launch_rope(op.dtype, A(op.out_off), nullptr, op.M, op.S, op.NH,
-                    op.HD, op.eps, os);
+                    op.HD, op.eps, os, 0, op.NKV);
         break;
       case kClip:
         // res_scale = min bound, q_scale = max bound

@@ -2,9 +2,18 @@ import re
 import subprocess
 import sys
 
+# usage: kernel_resources.py [--detail NAME_SUBSTRING] [file.hip ...]
+# --detail lists every instantiation whose mangled name contains the
+# substring on a line of its own (with scratch) instead of the grouped view.
+args = sys.argv[1:]
+detail = None
+if args[:1] == ["--detail"]:
+    detail, args = args[1], args[2:]
+srcs = args or ["csrc/kernels/conv.hip", "csrc/kernels/gemm.hip",
+                "csrc/kernels/attention.hip", "csrc/kernels/normalize.hip"]
+
 out = []
-for src in ["csrc/kernels/conv.hip", "csrc/kernels/gemm.hip",
-            "csrc/kernels/attention.hip", "csrc/kernels/normalize.hip"]:
+for src in srcs:
     r = subprocess.run(
         ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17",
          "-fPIC", "-I", "csrc", "-x", "hip",
@@ -27,6 +36,21 @@ for src in ["csrc/kernels/conv.hip", "csrc/kernels/gemm.hip",
     if cur:
         rows.append((cur, d))
     out.append((src, rows))
+
+if detail is not None:
+    for src, rows in out:
+        print(f"== {src}: instantiations matching '{detail}'")
+        for name, d in rows:
+            if detail in name:
+                print(f"  VGPR={d.get('VGPRs'):>4} AGPR={d.get('AGPRs'):>4} "
+                      f"SGPR={d.get('TotalSGPRs'):>4} "
+                      f"LDS={d.get('LDS Size [bytes/block]'):>7} "
+                      f"scratch={d.get('ScratchSize [bytes/lane]')} "
+                      f"occ/SIMD={d.get('Occupancy [waves/SIMD]')} "
+                      f"spills={d.get('VGPRs Spill')}/{d.get('SGPRs Spill')}"
+                      f"  {name}")
+        print()
+    sys.exit(0)
 
 print("Kernel resource usage (hipcc -Rpass-analysis=kernel-resource-usage, gfx950)")
 print("Spills are zero across every kernel; occupancy is LDS-bound for the")

@@ -23,6 +23,12 @@ biases; RoPE reads the device position counter, so the captured decode
 graph stays position-free); otherwise GPT-2 (LayerNorm + learned pos
 emb + GELU). prefill()/step()/verify_chunk() and the paged KV pool work
 for both.
+
+Grouped-query LLaMA graphs (`build_llama(kv_heads=...)`, attention nodes
+carrying `kv_heads`) run natively: the qkv projection is
+(heads + 2*kv_heads)*head_dim wide, the dense caches are
+[B][kv_heads][smax][head_dim] and paged pools hold kv_heads heads per
+position, so KV memory is heads/kv_heads x smaller than for MHA.
 """
 from __future__ import annotations
 
@@ -35,11 +41,13 @@ import numpy as np
 class PagedKVPool:
     """vLLM-style paged KV memory: ONE fixed physical pool per layer,
     shared by every slot, mapped through a per-slot device block table.
-    Pages hold 64 positions x heads x 64 dims; a page id is valid across
-    all layers (each layer has its own K/V pools, ids allocated in
-    lockstep), so one table serves the whole stack. Host-side free list;
-    idle/reset slots return their pages — parked sequences hold ZERO
-    cache memory (the paged payoff vs the dense [B][H][smax][64] layout).
+    Pages hold 64 positions x heads x head_dim, where `heads` is the
+    number of KV heads (= query heads for MHA, fewer for grouped-query
+    models); a page id is valid across all layers (each layer has its
+    own K/V pools, ids allocated in lockstep), so one table serves the
+    whole stack. Host-side free list; idle/reset slots return their
+    pages — parked sequences hold ZERO cache memory (the paged payoff vs
+    the dense [B][heads][smax][head_dim] layout).
     """
 
     def __init__(self, layers: int, heads: int, batch: int,
@@ -170,6 +178,9 @@ class DecodeSession:
         while f"l{li}_qkv" in nodes:
             att = nodes[f"l{li}_att"]
             self.heads = att.attrs["heads"]
+            # grouped-query: kv_heads < heads narrows the qkv row to
+            # (heads + 2*kv_heads)*hd and the caches to kv_heads
+            self.kv_heads = att.attrs.get("kv_heads") or self.heads
             self.hd = att.attrs.get("head_dim",
                                     self.hidden // self.heads)
             if self.hd not in (64, 128):
@@ -193,7 +204,7 @@ class DecodeSession:
                     n = nodes[f"l{li}_{key}"]
                     lay[key + "_w"] = dev16(n.attrs["weight"])
                     lay[key + "_b"] = dev32(n.attrs["bias"])
-            lay["kcache"] = torch.zeros(batch, self.heads, smax, self.hd,
+            lay["kcache"] = torch.zeros(batch, self.kv_heads, smax, self.hd,
                                         dtype=torch.half, device="cuda")
             lay["vcache"] = torch.zeros_like(lay["kcache"])
             self.layers.append(lay)
@@ -214,13 +225,17 @@ class DecodeSession:
         self.lm_head = lm_head  # logits = h @ tok^T (weight tying)
 
         B, Hd = batch, self.hidden
+        # fused qkv row width; att rows are heads*hd (== hidden here)
+        self.qkv_w = (self.heads + 2 * self.kv_heads) * self.hd
+        self._nkv = self.kv_heads if self.kv_heads != self.heads else 0
         self.ids = torch.zeros(B, dtype=torch.int32, device="cuda")
         self.pos = torch.zeros(B, dtype=torch.int32, device="cuda")
         self._slot_steps = np.zeros(B, np.int64)
         self._active = np.ones(B, bool)  # host mirror of pos[b] >= 0
         self.h = torch.zeros(B, Hd, dtype=torch.half, device="cuda")
         self.x = torch.zeros(B, Hd, dtype=torch.half, device="cuda")
-        self.qkv = torch.zeros(B, 3 * Hd, dtype=torch.half, device="cuda")
+        self.qkv = torch.zeros(B, self.qkv_w, dtype=torch.half,
+                               device="cuda")
         self.att = torch.zeros(B, Hd, dtype=torch.half, device="cuda")
         self.x2 = torch.zeros(B, Hd, dtype=torch.half, device="cuda")
         self.ff = torch.zeros(B, self.inter, dtype=torch.half, device="cuda")
@@ -246,17 +261,20 @@ class DecodeSession:
         if paged:
             mp = (smax + 63) // 64
             self.kv_pool = paged if isinstance(paged, PagedKVPool) else \
-                PagedKVPool(self.n_layers, self.heads, B,
+                PagedKVPool(self.n_layers, self.kv_heads, B,
                             num_pages=B * mp, max_pages_per_slot=mp,
                             device=device, head_dim=self.hd)
             if self.kv_pool.layers != self.n_layers or \
-                    self.kv_pool.heads != self.heads or \
+                    self.kv_pool.heads != self.kv_heads or \
                     getattr(self.kv_pool, "head_dim", 64) != self.hd:
                 raise ValueError("pool layer/head mismatch")
             for lay in self.layers:  # release the dense caches
                 lay["kcache"] = None
                 lay["vcache"] = None
         self.fused = bool(fused)
+        if self.fused and self._nkv:
+            raise ValueError("fused decode does not support grouped-query "
+                             "attention (kv_heads < heads)")
         if self.fused and self.arch != "gpt2":
             raise ValueError("fused decode supports the gpt2 recipe only")
         if self.fused and (B > 64 or not lm_head):
@@ -360,14 +378,14 @@ class DecodeSession:
         ops.kv_append(qkv_ptr, kc, vc, self.batch, self.heads, rows,
                       self.smax, pos=self.pos.data_ptr() if att_ptr else 0,
                       table=table, max_pages=mp, stream=s, sync=False,
-                      D=self.hd)
+                      D=self.hd, kv_heads=self._nkv)
         if att_ptr:
             scale = 1.0 / float(np.sqrt(float(self.hd)))
             ops.decode_attention(qkv_ptr, kc, vc, att_ptr,
                                  self.pos.data_ptr(), self.batch,
                                  self.heads, rows, self.smax, scale,
                                  table=table, max_pages=mp, stream=s,
-                                 sync=False, D=self.hd)
+                                 sync=False, D=self.hd, kv_heads=self._nkv)
 
     def _enqueue_llama(self):
         """One LLaMA decode step (pos-relative, captured like the gpt2
@@ -390,11 +408,11 @@ class DecodeSession:
                     B, Hd, eps=self.rms_eps, stream=s, sync=False)
         for li, lay in enumerate(self.layers):
             ops.gemm_bt(0, self.x.data_ptr(), lay["qkv_w"].data_ptr(),
-                        self.qkv.data_ptr(), M=B, N=3 * Hd, K=Hd,
+                        self.qkv.data_ptr(), M=B, N=self.qkv_w, K=Hd,
                         epi=self._epi_none, stream=s, sync=False, tile=T4)
             ops.rope(0, self.qkv.data_ptr(), pos=self.pos.data_ptr(), M=B,
                      S=self.smax, H=self.heads, D=self.hd, theta=self.theta,
-                     stream=s, sync=False)
+                     stream=s, sync=False, kv_heads=self._nkv)
             self._kv(li, lay, self.qkv.data_ptr(), 1, self.att.data_ptr())
             ops.gemm_bt(0, self.att.data_ptr(), lay["proj_w"].data_ptr(),
                         self.x2.data_ptr(), M=B, N=Hd, K=Hd,
@@ -541,7 +559,7 @@ class DecodeSession:
         h = torch.empty(M, Hd, dtype=torch.half, device="cuda")
         x = torch.empty(M, Hd, dtype=torch.half, device="cuda")
         x2 = torch.empty(M, Hd, dtype=torch.half, device="cuda")
-        qkv = torch.empty(M, 3 * Hd, dtype=torch.half, device="cuda")
+        qkv = torch.empty(M, self.qkv_w, dtype=torch.half, device="cuda")
         ff = torch.empty(M, inter, dtype=torch.half, device="cuda")
         ff2 = (torch.empty(M, inter, dtype=torch.half, device="cuda")
                if self.arch == "llama" else None)
@@ -557,16 +575,17 @@ class DecodeSession:
                         M, Hd, eps=self.rms_eps, stream=s, sync=False)
             for li, lay in enumerate(self.layers):
                 ops.gemm_bt(0, x.data_ptr(), lay["qkv_w"].data_ptr(),
-                            qkv.data_ptr(), M=M, N=3 * Hd, K=Hd,
+                            qkv.data_ptr(), M=M, N=self.qkv_w, K=Hd,
                             epi=self._epi_none, stream=s, sync=False)
                 # full-sequence rope: pos = row % Pp (exact for rows < P;
                 # padded tail is causal-masked / overwritten before read)
                 ops.rope(0, qkv.data_ptr(), M=M, S=Pp, H=self.heads,
-                         D=self.hd, theta=self.theta, stream=s, sync=False)
+                         D=self.hd, theta=self.theta, stream=s, sync=False,
+                         kv_heads=self._nkv)
                 self._kv(li, lay, qkv.data_ptr(), Pp)
                 ops.attention(0, qkv.data_ptr(), x2.data_ptr(), B, Pp,
                               self.heads, self.hd, scale, stream=s,
-                              sync=False, causal=1)
+                              sync=False, causal=1, kv_heads=self._nkv)
                 ops.gemm_bt(0, x2.data_ptr(), lay["proj_w"].data_ptr(),
                             x.data_ptr(), M=M, N=Hd, K=Hd,
                             epi=self._epi_none, stream=s, sync=False)
@@ -716,12 +735,13 @@ class DecodeSession:
                         cb["x"].data_ptr(), M, Hd, eps=self.rms_eps, stream=s, sync=False)
             for li, lay in enumerate(self.layers):
                 ops.gemm_bt(0, cb["x"].data_ptr(), lay["qkv_w"].data_ptr(),
-                            cb["qkv"].data_ptr(), M=M, N=3 * Hd, K=Hd,
+                            cb["qkv"].data_ptr(), M=M, N=self.qkv_w, K=Hd,
                             epi=self._epi_none, stream=s, sync=False)
                 # chunk rope: row b*K+i rotates at pos[b] + i
                 ops.rope(0, cb["qkv"].data_ptr(), pos=self.pos.data_ptr(),
                          M=M, S=self.smax, H=self.heads, D=self.hd,
-                         theta=self.theta, stream=s, sync=False, chunk=K)
+                         theta=self.theta, stream=s, sync=False, chunk=K,
+                         kv_heads=self._nkv)
                 self._kv(li, lay, cb["qkv"].data_ptr(), K,
                          cb["att"].data_ptr())
                 ops.gemm_bt(0, cb["att"].data_ptr(),
@@ -846,7 +866,8 @@ class DecodeSession:
                 h=torch.zeros(M, Hd, dtype=torch.half, device="cuda"),
                 x=torch.zeros(M, Hd, dtype=torch.half, device="cuda"),
                 x2=torch.zeros(M, Hd, dtype=torch.half, device="cuda"),
-                qkv=torch.zeros(M, 3 * Hd, dtype=torch.half, device="cuda"),
+                qkv=torch.zeros(M, self.qkv_w, dtype=torch.half,
+                                device="cuda"),
                 att=torch.zeros(M, Hd, dtype=torch.half, device="cuda"),
                 ff=torch.zeros(M, inter, dtype=torch.half, device="cuda"),
                 ff2=(torch.zeros(M, inter, dtype=torch.half, device="cuda")

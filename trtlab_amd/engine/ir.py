@@ -206,12 +206,22 @@ class Graph:
                           name)
 
     def rope(self, qkv: str, heads: int, seq: int, theta: float = 10000.0,
-             name: Optional[str] = None) -> str:
+             name: Optional[str] = None,
+             kv_heads: Optional[int] = None) -> str:
         """Rotary position embedding applied to the q/k blocks of fused
         qkv rows (in place — the planner aliases output and input in the
-        arena). LLaMA-style half-split rotation, angle base `theta`."""
-        return self._emit("rope", [qkv], self.tensors[qkv].shape,
-                          dict(heads=heads, seq=seq, theta=float(theta)),
+        arena). LLaMA-style half-split rotation, angle base `theta`.
+        kv_heads (grouped-query attention): the rows are
+        [q: heads | k: kv_heads | v: kv_heads] head blocks; None = heads."""
+        attrs = dict(heads=heads, seq=seq, theta=float(theta))
+        if kv_heads:
+            width = self.tensors[qkv].shape[1]
+            assert heads % kv_heads == 0 and kv_heads <= heads, \
+                f"rope: heads {heads} not a multiple of kv_heads {kv_heads}"
+            assert width % (heads + 2 * kv_heads) == 0, \
+                f"rope: width {width} vs heads {heads} + 2*{kv_heads}"
+            attrs["kv_heads"] = int(kv_heads)
+        return self._emit("rope", [qkv], self.tensors[qkv].shape, attrs,
                           name)
 
     def view(self, x: str, shape: Tuple[int, ...],
@@ -261,11 +271,27 @@ class Graph:
     def attention(self, qkv: str, heads: int, seq: int,
                   varlen: bool = False, pad_id: int = 0,
                   causal: bool = False,
-                  name: Optional[str] = None) -> str:
+                  name: Optional[str] = None,
+                  kv_heads: Optional[int] = None) -> str:
         """varlen: mask keys beyond each sequence's valid length (derived
         from right-padded token ids; requires an i32 ids graph input).
-        causal: decoder-style key > query masking (GPT-family)."""
+        causal: decoder-style key > query masking (GPT-family).
+        kv_heads (grouped-query attention): qkv rows are
+        [q: heads*D | k: kv_heads*D | v: kv_heads*D] and query head h
+        attends kv head h // (heads // kv_heads); None = heads (MHA)."""
         m, k3 = self.tensors[qkv].shape
+        if kv_heads:
+            assert heads % kv_heads == 0 and kv_heads <= heads, \
+                f"attention: heads {heads} not a multiple of kv_heads " \
+                f"{kv_heads}"
+            assert k3 % (heads + 2 * kv_heads) == 0, \
+                f"attention: width {k3} vs heads {heads} + 2*{kv_heads}"
+            hd = k3 // (heads + 2 * kv_heads)
+            return self._emit("attention", [qkv], (m, heads * hd),
+                              dict(heads=heads, seq=seq, head_dim=hd,
+                                   varlen=varlen, pad_id=pad_id,
+                                   causal=causal, kv_heads=int(kv_heads)),
+                              name)
         hid = k3 // 3
         return self._emit("attention", [qkv], (m, hid),
                           dict(heads=heads, seq=seq, head_dim=hid // heads,

@@ -274,7 +274,8 @@ def import_onnx(data: bytes, batch: Optional[int] = None,
                               seq=int(attrs["seq"]),
                               causal=bool(attrs.get("causal", 0)),
                               varlen=bool(attrs.get("varlen", 0)),
-                              pad_id=int(attrs.get("pad_id", 0)))
+                              pad_id=int(attrs.get("pad_id", 0)),
+                              kv_heads=int(attrs.get("kv_heads", 0)) or None)
         elif op == "TrtlabRMSNorm":
             out = g.rmsnorm(x, inits[ins[1]].astype(np.float32),
                             eps=float(attrs.get("epsilon", 1e-5)))
@@ -283,7 +284,8 @@ def import_onnx(data: bytes, batch: Optional[int] = None,
         elif op == "TrtlabRope":
             out = g.rope(x, heads=int(attrs["heads"]),
                          seq=int(attrs["seq"]),
-                         theta=float(attrs.get("theta", 10000.0)))
+                         theta=float(attrs.get("theta", 10000.0)),
+                         kv_heads=int(attrs.get("kv_heads", 0)) or None)
         else:
             raise ValueError(f"ONNX op {op} not supported by the importer")
         remap[outs[0]] = out
@@ -440,7 +442,9 @@ def export_onnx(g: Graph) -> bytes:
                            _attr_i("seq", a["seq"]),
                            _attr_i("causal", 1 if a.get("causal") else 0),
                            _attr_i("varlen", 1 if a.get("varlen") else 0),
-                           _attr_i("pad_id", a.get("pad_id", 0)))
+                           _attr_i("pad_id", a.get("pad_id", 0)),
+                           *([_attr_i("kv_heads", a["kv_heads"])]
+                             if a.get("kv_heads") else []))
         elif n.kind == "view":
             # Reshape with the target shape as an int64 initializer
             shp = np.asarray(g.tensors[n.output].shape, np.int64)
@@ -462,7 +466,9 @@ def export_onnx(g: Graph) -> bytes:
             nodes += _node("TrtlabRope", [n.inputs[0]], [n.output],
                            _attr_i("heads", a["heads"]),
                            _attr_i("seq", a["seq"]),
-                           _attr_f("theta", a["theta"]))
+                           _attr_f("theta", a["theta"]),
+                           *([_attr_i("kv_heads", a["kv_heads"])]
+                             if a.get("kv_heads") else []))
         else:
             raise ValueError(f"export: unsupported node kind {n.kind}")
 

@@ -813,6 +813,8 @@ class Planner:
                          epi=op.params.get("out_dtype", 0),
                          q_scale=op.params.get("q_scale", 0.0),
                          causal=1 if op.params.get("causal") else 0)
+                if op.params.get("kv_heads"):  # grouped-query only
+                    d["NKV"] = int(op.params["kv_heads"])
             elif op.kind == K_RMSNORM:
                 m, ncol = shapes[op.inputs[0]]
                 d.update(kind=K_RMSNORM, M=m, N=ncol, eps=op.params["eps"])
@@ -824,11 +826,14 @@ class Planner:
             elif op.kind == K_ROPE:
                 m, n3 = shapes[op.inputs[0]]
                 heads = op.params["heads"]
-                hd = n3 // (3 * heads)
+                nkv = op.params.get("kv_heads")
+                hd = n3 // (heads + 2 * nkv) if nkv else n3 // (3 * heads)
                 # eps carries theta; the op runs IN PLACE on the aliased
                 # arena buffer (out_off == in_off by construction below)
                 d.update(kind=K_ROPE, M=m, S=op.params["seq"], NH=heads,
                          HD=hd, eps=op.params["theta"])
+                if nkv:  # grouped-query only
+                    d["NKV"] = int(nkv)
             elif op.kind == K_CLIP:
                 n = 1
                 for s_ in shapes[op.output]:

@@ -225,10 +225,19 @@ def run_reference(plan: EnginePlan, input_nhwc, return_all: bool = False):
         elif op.kind == K_ATTENTION:
             b, s, nh, hd = d["B"], d["S"], d["NH"], d["HD"]
             hid = nh * hd
-            qkv = x.reshape(b, s, 3, nh, hd)
-            q = qkv[:, :, 0].permute(0, 2, 1, 3)  # [B, NH, S, HD]
-            k = qkv[:, :, 1].permute(0, 2, 1, 3)
-            v = qkv[:, :, 2].permute(0, 2, 1, 3)
+            if d.get("NKV"):  # grouped-query: q head h uses kv head h // G
+                nkv = d["NKV"]
+                xr = x.reshape(b, s, (nh + 2 * nkv), hd)
+                q = xr[:, :, :nh].permute(0, 2, 1, 3)
+                k = xr[:, :, nh:nh + nkv].permute(0, 2, 1, 3) \
+                    .repeat_interleave(nh // nkv, dim=1)
+                v = xr[:, :, nh + nkv:].permute(0, 2, 1, 3) \
+                    .repeat_interleave(nh // nkv, dim=1)
+            else:
+                qkv = x.reshape(b, s, 3, nh, hd)
+                q = qkv[:, :, 0].permute(0, 2, 1, 3)  # [B, NH, S, HD]
+                k = qkv[:, :, 1].permute(0, 2, 1, 3)
+                v = qkv[:, :, 2].permute(0, 2, 1, 3)
             scores = q @ k.transpose(-1, -2) * d["att_scale"]
             if len(op.inputs) > 1:  # varlen: mask right-padded keys
                 lens = t[op.inputs[1]].long()
@@ -261,15 +270,17 @@ def run_reference(plan: EnginePlan, input_nhwc, return_all: bool = False):
             sin = torch.sin(ang).float()
             y = x.clone()
             hid = heads * hd
-            for blk in range(2):  # q then k; v untouched
-                base = blk * hid
-                v = x[:, base:base + hid].reshape(m, heads, hd)
+            nkv = d.get("NKV") or heads  # k block holds NKV heads (GQA)
+            # q then k; v untouched
+            for base, nh_ in ((0, heads), (hid, nkv)):
+                w_ = nh_ * hd
+                v = x[:, base:base + w_].reshape(m, nh_, hd)
                 x0 = v[..., :half]
                 x1 = v[..., half:]
                 r0 = x0 * cos[:, None, :] - x1 * sin[:, None, :]
                 r1 = x0 * sin[:, None, :] + x1 * cos[:, None, :]
-                y[:, base:base + hid] = torch.cat([r0, r1], -1).reshape(
-                    m, hid)
+                y[:, base:base + w_] = torch.cat([r0, r1], -1).reshape(
+                    m, w_)
             t[op.output] = y
         elif op.kind == K_CLIP:
             t[op.output] = torch.clamp(x, d["res_scale"], d["q_scale"])

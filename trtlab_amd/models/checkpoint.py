@@ -21,7 +21,11 @@ GQA checkpoints (num_key_value_heads < num_attention_heads) are
 loaded by replicating each kv head's k/v projection rows across its
 query group — numerically IDENTICAL to grouped attention (every query
 head in group g attends the same k/v), traded for MHA-sized KV cache
-(a fine trade against 288 GB of HBM3E per GPU).
+(a fine trade against 288 GB of HBM3E per GPU). native_gqa=True keeps
+the k/v projections unexpanded instead and builds grouped-query
+rope/attention nodes (kv_heads = num_key_value_heads): the qkv
+projection, the KV caches and the decode attention's K/V traffic all
+shrink by heads / kv_heads.
 """
 from __future__ import annotations
 
@@ -68,9 +72,12 @@ def _read_config(path: str) -> dict:
 def build_llama_from_safetensors(path: str, batch: int = 1,
                                  seq: int = 256,
                                  heads: Optional[int] = None,
-                                 theta: Optional[float] = None) -> Graph:
+                                 theta: Optional[float] = None,
+                                 native_gqa: bool = False) -> Graph:
     """Load HF LLaMA weights and build the engine IR graph around them.
-    heads/theta default from config.json next to the checkpoint."""
+    heads/theta default from config.json next to the checkpoint.
+    native_gqa=False replicates a GQA checkpoint's kv heads to MHA (see
+    the module docstring); True keeps them grouped."""
     state = _load_state(path)
     cfg = _read_config(path)
     heads = heads or cfg.get("num_attention_heads")
@@ -81,6 +88,7 @@ def build_llama_from_safetensors(path: str, batch: int = 1,
         raise ValueError(f"heads {heads} not divisible by kv heads {kvh}")
     theta = theta or float(cfg.get("rope_theta", 10000.0))
     eps = float(cfg.get("rms_norm_eps", 1e-5))
+    gqa = kvh if native_gqa and kvh != heads else None
 
     tok = state["model.embed_tokens.weight"]  # [V, H]
     vocab, hidden = tok.shape
@@ -107,7 +115,7 @@ def build_llama_from_safetensors(path: str, batch: int = 1,
             # GQA -> MHA: repeat each kv head's hd-row block across its
             # query group (exact — same k/v seen by every head in the
             # group, rope rotation depends only on the in-head dim)
-            if kvh == heads:
+            if kvh == heads or native_gqa:
                 return w
             r = heads // kvh
             blocks = w.reshape(kvh, hd, w.shape[1])
@@ -119,9 +127,9 @@ def build_llama_from_safetensors(path: str, batch: int = 1,
              expand_kv(state[pre + "self_attn.v_proj.weight"])], axis=0)
         qkv = g.gemm(x, qkv_w, None, name=f"l{li}_qkv")
         qkv = g.rope(qkv, heads=heads, seq=seq, theta=theta,
-                     name=f"l{li}_rope")
+                     name=f"l{li}_rope", kv_heads=gqa)
         att = g.attention(qkv, heads=heads, seq=seq, causal=True,
-                          name=f"l{li}_att")
+                          name=f"l{li}_att", kv_heads=gqa)
         proj = g.gemm(att, state[pre + "self_attn.o_proj.weight"], None,
                       name=f"l{li}_proj")
         h = g.add(h, proj, name=f"l{li}_res1")

@@ -14,12 +14,19 @@ from trtlab_amd.engine.ir import Graph
 def build_llama(batch: int = 1, seq: int = 256, hidden: int = 1024,
                 layers: int = 4, heads: int = 8, seed: int = 0,
                 vocab: int = 32000, theta: float = 10000.0,
-                intermediate: int | None = None) -> Graph:
+                intermediate: int | None = None,
+                kv_heads: int | None = None) -> Graph:
     """head_dim = hidden // heads must be 64 or 128 (attention kernels).
     Input: int32 token ids [B*S]; output: final RMS-normed hidden states
-    [B*S, hidden] (weight-tied scoring is hidden @ tok^T, as in GPT-2)."""
+    [B*S, hidden] (weight-tied scoring is hidden @ tok^T, as in GPT-2).
+    kv_heads: grouped-query attention with that many kv heads (must
+    divide heads); the qkv weight is [(heads + 2*kv_heads)*hd, hidden]
+    and the KV caches shrink by heads / kv_heads. None = MHA."""
     hd = hidden // heads
     assert hidden % heads == 0 and hd in (64, 128), "head_dim must be 64/128"
+    assert not kv_heads or (heads % kv_heads == 0 and kv_heads <= heads), \
+        "heads must be a multiple of kv_heads"
+    qkv_rows = (heads + 2 * kv_heads) * hd if kv_heads else 3 * hidden
     inter = intermediate or int(round(hidden * 8 / 3 / 64) * 64)
     rng = np.random.RandomState(seed)
 
@@ -37,11 +44,11 @@ def build_llama(batch: int = 1, seq: int = 256, hidden: int = 1024,
     for li in range(layers):
         gam1 = (rng.uniform(0.9, 1.1, hidden)).astype(np.float32)
         x = g.rmsnorm(h, gam1, name=f"l{li}_rms1")
-        qkv = g.gemm(x, w(3 * hidden, hidden), None, name=f"l{li}_qkv")
+        qkv = g.gemm(x, w(qkv_rows, hidden), None, name=f"l{li}_qkv")
         qkv = g.rope(qkv, heads=heads, seq=seq, theta=theta,
-                     name=f"l{li}_rope")
+                     name=f"l{li}_rope", kv_heads=kv_heads)
         att = g.attention(qkv, heads=heads, seq=seq, causal=True,
-                          name=f"l{li}_att")
+                          name=f"l{li}_att", kv_heads=kv_heads)
         proj = g.gemm(att, w(hidden, hidden), None, name=f"l{li}_proj")
         h = g.add(h, proj, name=f"l{li}_res1")
         gam2 = (rng.uniform(0.9, 1.1, hidden)).astype(np.float32)
