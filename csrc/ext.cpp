@@ -561,6 +561,21 @@ PYBIND11_MODULE(_C, m) {
           py::arg("x"), py::arg("out"), py::arg("temps") = 0,
           py::arg("seeds") = 0, py::arg("pos") = 0, py::arg("M") = 0,
           py::arg("V") = 0, py::arg("stream") = 0, py::arg("sync") = true);
+  ops.def("topk_topp_sample_rows",
+          [](uintptr_t x, uintptr_t out, uintptr_t temps, uintptr_t top_k,
+             uintptr_t top_p, uintptr_t seeds, uintptr_t pos, int M, int V,
+             uintptr_t kept, uintptr_t thr, uintptr_t stream, bool sync) {
+            launch_topk_topp_sample_rows(
+                (void*)x, (void*)out, (void*)temps, (void*)top_k,
+                (void*)top_p, (void*)seeds, (void*)pos, (void*)kept,
+                (void*)thr, M, V, as_stream(stream));
+            if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
+          },
+          py::arg("x"), py::arg("out"), py::arg("temps") = 0,
+          py::arg("top_k") = 0, py::arg("top_p") = 0, py::arg("seeds") = 0,
+          py::arg("pos") = 0, py::arg("M") = 0, py::arg("V") = 0,
+          py::arg("kept") = 0, py::arg("thr") = 0, py::arg("stream") = 0,
+          py::arg("sync") = true);
   ops.def("channel_affine",
           [](int dtype, uintptr_t x, uintptr_t out, uintptr_t s,
              uintptr_t b, int64_t M, int C, bool relu, uintptr_t stream,

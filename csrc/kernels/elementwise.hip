@@ -4,6 +4,7 @@
 #include <hip/hip_fp8.h>
 
 #include "../common.h"
+#include "sampling_common.h"
 
 namespace trtlab {
 
@@ -507,7 +508,6 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(
   int row = blockIdx.x;
   if (row >= M) return;
   const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
   const _Float16* r = x + (int64_t)row * V;
   float best = -1e30f;
   int bi = 0x7fffffff;
@@ -533,30 +533,10 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(
       bi = c;
     }
   }
-#pragma unroll
-  for (int off = 32; off; off >>= 1) {
-    float ob = __shfl_xor(best, off, 64);
-    int oi = __shfl_xor(bi, off, 64);
-    if (ob > best || (ob == best && oi < bi)) {
-      best = ob;
-      bi = oi;
-    }
-  }
   __shared__ float wb[4];
   __shared__ int wi[4];
-  if (lane == 0) {
-    wb[wave] = best;
-    wi[wave] = bi;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < 4; ++w)
-      if (wb[w] > wb[0] || (wb[w] == wb[0] && wi[w] < wi[0])) {
-        wb[0] = wb[w];
-        wi[0] = wi[w];
-      }
-    out[row] = wi[0];
-  }
+  block_argmax_256(best, bi, wb, wi);
+  if (tid == 0) out[row] = wi[0];
 }
 
 void launch_argmax_rows(const void* x, void* out, int M, int V,
@@ -573,13 +553,8 @@ void launch_argmax_rows(const void* x, void* out, int M, int V,
 // DEVICE position counter, so every decode step draws fresh noise even
 // inside a captured graph. temps[row] <= 0 degrades to plain greedy
 // argmax (one kernel serves mixed greedy/sampled batches).
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-  z += 0x9e3779b97f4a7c15ull;
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
-
+// (splitmix64, the noise and the block reduction live in sampling_common.h,
+// shared with sampling.hip.)
 __global__ __launch_bounds__(256) void gumbel_argmax_rows_kernel(
     const _Float16* __restrict__ x, int* __restrict__ out,
     const float* __restrict__ temps, const int* __restrict__ seeds,
@@ -587,53 +562,21 @@ __global__ __launch_bounds__(256) void gumbel_argmax_rows_kernel(
   int row = blockIdx.x;
   if (row >= M) return;
   const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
   const _Float16* r = x + (int64_t)row * V;
   const float T = temps ? temps[row] : 0.0f;
   const float invT = (T > 0.0f) ? 1.0f / T : 0.0f;
-  const uint64_t key =
-      ((uint64_t)(uint32_t)(seeds ? seeds[row] : 0) << 32) ^
-      (uint64_t)(uint32_t)(pos ? pos[row] : 0) ^
-      ((uint64_t)(uint32_t)row << 20);
+  const uint64_t key = gumbel_row_key(seeds, pos, row);
   float best = -1e30f;
   int bi = 0x7fffffff;
   for (int c = tid; c < V; c += 256) {
     float v = (float)r[c];
-    if (T > 0.0f) {
-      uint64_t h = splitmix64(key ^ (uint64_t)c);
-      // u in (0, 1): top 24 bits, never exactly 0
-      float u = ((float)(uint32_t)(h >> 40) + 0.5f) * (1.0f / 16777216.f);
-      v = v * invT - __logf(-__logf(u));
-    }
-    if (v > best || (v == best && c < bi)) {
-      best = v;
-      bi = c;
-    }
-  }
-#pragma unroll
-  for (int off = 32; off; off >>= 1) {
-    float ob = __shfl_xor(best, off, 64);
-    int oi = __shfl_xor(bi, off, 64);
-    if (ob > best || (ob == best && oi < bi)) {
-      best = ob;
-      bi = oi;
-    }
+    if (T > 0.0f) v = gumbel_perturb(v, invT, key, c);
+    argmax_take(v, c, best, bi);
   }
   __shared__ float wb[4];
   __shared__ int wi[4];
-  if (lane == 0) {
-    wb[wave] = best;
-    wi[wave] = bi;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < 4; ++w)
-      if (wb[w] > wb[0] || (wb[w] == wb[0] && wi[w] < wi[0])) {
-        wb[0] = wb[w];
-        wi[0] = wi[w];
-      }
-    out[row] = wi[0];
-  }
+  block_argmax_256(best, bi, wb, wi);
+  if (tid == 0) out[row] = wi[0];
 }
 
 void launch_gumbel_argmax_rows(const void* x, void* out, const void* temps,

@@ -88,6 +88,16 @@ void launch_argmax_rows(const void* x, void* out, int M, int V,
 void launch_gumbel_argmax_rows(const void* x, void* out, const void* temps,
                                const void* seeds, const void* pos, int M,
                                int V, hipStream_t stream);
+// Top-k / nucleus sampling (sampling.hip): the Gumbel-max draw of
+// gumbel_argmax_rows restricted to the value-class candidate set of
+// (top_k[row], top_p[row]); with neither filter active the result is that
+// kernel's. kept (int32 [M], size of the set) and thr (float [M],
+// threshold logit) are optional: null skips them.
+void launch_topk_topp_sample_rows(const void* x, void* out, const void* temps,
+                                  const void* top_k, const void* top_p,
+                                  const void* seeds, const void* pos,
+                                  void* kept, void* thr, int M, int V,
+                                  hipStream_t stream);
 void launch_clip(int dtype, const void* in, void* out, int64_t n, float mn,
                  float mx, hipStream_t stream);
 void launch_transpose2d(int dtype, const void* in, void* out, int M, int N,

@@ -39,7 +39,7 @@ def serve(args):
                        hidden=args.hidden or 768, layers=args.layers,
                        seed=0, embeddings=True)
     sess = DecodeSession(g, batch=args.batch, smax=args.smax, lm_head=True)
-    svc = GenerationService(sess)
+    svc = GenerationService(sess, device_truncation=args.device_sampling)
     srv = Server(f"0.0.0.0:{args.port}")
     srv.register_service(svc.service)
     srv.async_start()
@@ -94,6 +94,9 @@ def main():
     ap.add_argument("--top-k", type=int, default=0)
     ap.add_argument("--top-p", type=float, default=0.0)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device-sampling", action="store_true",
+                    help="server: sample top-k / top-p streams on the GPU "
+                         "too (no logits row leaves the device)")
     args = ap.parse_args()
     client(args) if args.client else serve(args)
 

@@ -24,6 +24,7 @@ SOURCES = [
     "csrc/kernels/pool.hip",
     "csrc/kernels/normalize.hip",
     "csrc/kernels/elementwise.hip",
+    "csrc/kernels/sampling.hip",
     "csrc/kernels/attention.hip",
     "csrc/kernels/embedding.hip",
     "csrc/runtime/memory.cpp",
@@ -38,6 +39,7 @@ HEADERS = [
     "csrc/kernels/gemm_common.h",
     "csrc/kernels/mx_common.h",
     "csrc/kernels/launchers.h",
+    "csrc/kernels/sampling_common.h",
     "csrc/runtime/runtime.h",
     "csrc/runtime/comm.h",
 ]

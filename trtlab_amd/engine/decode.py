@@ -32,7 +32,7 @@ position, so KV memory is heads/kv_heads x smaller than for MHA.
 """
 from __future__ import annotations
 
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import numpy as np
 
@@ -252,6 +252,8 @@ class DecodeSession:
         self.gids = (torch.zeros(B, dtype=torch.int32, device="cuda")
                      if lm_head else None)
         self.supports_ids = lm_head
+        # sample_tokens(..., top_k, top_p): device-side top-k / nucleus
+        self.supports_truncation = lm_head
         self.h2 = torch.zeros(B, Hd, dtype=torch.half, device="cuda")
         # paged KV mode: paged = a PagedKVPool (shared with other
         # sessions) or True (private pool sized for smax). The dense
@@ -898,14 +900,22 @@ class DecodeSession:
             return cb["gids"].cpu().numpy().reshape(B, K)
         return cb["logits"].float().cpu().numpy().reshape(B, K, self.vocab)
 
-    def sample_tokens(self, temps: np.ndarray,
-                      seeds: np.ndarray) -> np.ndarray:
+    def sample_tokens(self, temps: np.ndarray, seeds: np.ndarray,
+                      top_k: Optional[np.ndarray] = None,
+                      top_p: Optional[np.ndarray] = None) -> np.ndarray:
         """Device-side temperature sampling of the LAST step's logits
         (Gumbel-max: an exact softmax(logits/T) categorical draw per
         slot; temps[b] <= 0 degrades to greedy argmax). Noise is keyed
         (seeds[b], device pos[b], index), so consecutive steps draw
         fresh noise and a (seed, position) pair replays identically.
-        Only B ints cross PCIe."""
+        Only B ints cross PCIe.
+
+        top_k / top_p (per-slot int32 / float32 arrays, either may be
+        None = off for every slot) restrict each slot's draw to its
+        top-k / nucleus candidate set on the device
+        (ops.topk_topp_sample_rows; the rule is engine/sampling.py's
+        truncation_reference). A slot with top_k[b] <= 0 and top_p[b]
+        outside (0, 1) draws exactly what it draws with both None."""
         if self.logits is None:
             raise RuntimeError("sample_tokens requires lm_head=True")
         torch = self._torch
@@ -920,9 +930,33 @@ class DecodeSession:
         self._C.memory.memcpy_h2d(self._seeds_dev.data_ptr(),
                                   np.ascontiguousarray(seeds, np.int32),
                                   self.batch * 4)
-        self._C.ops.gumbel_argmax_rows(
+        if top_k is None and top_p is None:
+            self._C.ops.gumbel_argmax_rows(
+                self.logits.data_ptr(), self.gids.data_ptr(),
+                temps=self._temps_dev.data_ptr(),
+                seeds=self._seeds_dev.data_ptr(), pos=self.pos.data_ptr(),
+                M=self.batch, V=self.vocab, stream=self.stream, sync=True)
+            return self.gids.cpu().numpy()
+        if getattr(self, "_topk_dev", None) is None:
+            self._topk_dev = torch.zeros(self.batch, dtype=torch.int32,
+                                         device="cuda")
+            self._topp_dev = torch.zeros(self.batch, dtype=torch.float32,
+                                         device="cuda")
+        top_k = np.ascontiguousarray(
+            np.zeros(self.batch) if top_k is None else top_k, np.int32)
+        top_p = np.ascontiguousarray(
+            np.zeros(self.batch) if top_p is None else top_p, np.float32)
+        if top_k.size != self.batch or top_p.size != self.batch:
+            raise ValueError("top_k / top_p need one entry per slot")
+        self._C.memory.memcpy_h2d(self._topk_dev.data_ptr(), top_k,
+                                  self.batch * 4)
+        self._C.memory.memcpy_h2d(self._topp_dev.data_ptr(), top_p,
+                                  self.batch * 4)
+        self._C.ops.topk_topp_sample_rows(
             self.logits.data_ptr(), self.gids.data_ptr(),
             temps=self._temps_dev.data_ptr(),
+            top_k=self._topk_dev.data_ptr(),
+            top_p=self._topp_dev.data_ptr(),
             seeds=self._seeds_dev.data_ptr(), pos=self.pos.data_ptr(),
             M=self.batch, V=self.vocab, stream=self.stream, sync=True)
         return self.gids.cpu().numpy()

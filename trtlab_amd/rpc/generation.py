@@ -67,8 +67,15 @@ class GenerationEngine:
     """Continuous-batching loop over a lockstep decode session."""
 
     def __init__(self, session, eos: int = -1, inline_step: bool = False,
-                 max_waiting: int = 0):
-        """inline_step=True runs session.step() directly on the event
+                 max_waiting: int = 0, device_truncation: bool = False):
+        """device_truncation=True samples top-k / nucleus streams on the
+        device too (session.sample_tokens with per-slot top_k / top_p)
+        when the session advertises supports_truncation, so no logits
+        row leaves the GPU. Opt-in: such a stream's tokens for a given
+        seed then come from the device RNG, not the host one (the
+        distribution, and same seed => same stream, hold either way).
+
+        inline_step=True runs session.step() directly on the event
         loop instead of a worker thread. MEASURED COUNTERPRODUCTIVE
         (tools/gen_load.py, MI355X, 16 streams/8 slots): 5,491 -> 1,229
         tok/s. The worker-thread hop YIELDS the event loop for the whole
@@ -86,6 +93,8 @@ class GenerationEngine:
         # submit() raises OverflowError (the service maps it to
         # RESOURCE_EXHAUSTED) instead of queueing unboundedly
         self.max_waiting = int(max_waiting)
+        self.device_truncation = bool(device_truncation) and bool(
+            getattr(session, "supports_truncation", False))
         self._slots: List[Optional[dict]] = [None] * self.B
         self._free: List[int] = list(range(self.B))
         self._pending: collections.deque = collections.deque()
@@ -239,10 +248,12 @@ class GenerationEngine:
             # device fast path: greedy uses the in-graph argmax head;
             # plain-temperature sampling uses the Gumbel-max kernel on
             # the resident logits — either way only B ints cross PCIe.
-            # top-k / nucleus streams still need their logits rows.
+            # top-k / nucleus streams still need their logits rows,
+            # unless device_truncation hands them to the device sampler.
+            filtered = any(snap[b]["top_k"] != 0 or
+                           snap[b]["top_p"] != 0.0 for b in active)
             ids_only = (getattr(self.session, "supports_ids", False) and
-                        all(snap[b]["top_k"] == 0 and
-                            snap[b]["top_p"] == 0.0 for b in active))
+                        (self.device_truncation or not filtered))
             if ids_only:
                 sampled = any(snap[b]["temperature"] > 0.0 for b in active)
                 temps = np.zeros(self.B, np.float32)
@@ -250,11 +261,21 @@ class GenerationEngine:
                 for b in active:
                     temps[b] = max(snap[b]["temperature"], 0.0)
                     seeds[b] = snap[b].get("seed", 0)
+                # filter arrays only when a stream has a filter: the
+                # no-filter call stays exactly the two-argument one
+                trunc = ()
+                if filtered:
+                    top_k = np.zeros(self.B, np.int32)
+                    top_p = np.zeros(self.B, np.float32)
+                    for b in active:
+                        top_k[b] = snap[b]["top_k"]
+                        top_p[b] = snap[b]["top_p"]
+                    trunc = (top_k, top_p)
 
                 def _dev_step():
                     g = self.session.step(ids, return_ids=True)
                     if sampled:
-                        g = self.session.sample_tokens(temps, seeds)
+                        g = self.session.sample_tokens(temps, seeds, *trunc)
                     return g
 
                 if self.inline_step:
@@ -292,12 +313,14 @@ class GenerationService:
 
     def __init__(self, session, eos: int = -1,
                  name: str = "trtlab.gen.Generation",
-                 inline_step: bool = False, max_waiting: int = 0):
+                 inline_step: bool = False, max_waiting: int = 0,
+                 device_truncation: bool = False):
         from trtlab_amd.rpc.server import StreamingService
 
         self.engine = GenerationEngine(session, eos=eos,
                                        inline_step=inline_step,
-                                       max_waiting=max_waiting)
+                                       max_waiting=max_waiting,
+                                       device_truncation=device_truncation)
         svc = StreamingService(name)
         svc.register_streaming("Generate", self._generate, GenerateRequest,
                                GenerateToken)
