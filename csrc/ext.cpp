@@ -384,14 +384,15 @@ PYBIND11_MODULE(_C, m) {
              uintptr_t scale, uintptr_t bias, uintptr_t residual,
              uintptr_t zero_page, int Nb, int H, int W, int C, int Cout,
              int KH, int KW, int sh, int sw, int ph, int pw, int epi,
-             uintptr_t stream, bool sync, int tile, float res_scale) {
+             uintptr_t stream, bool sync, int tile, float res_scale,
+             int staging) {
             launch_conv2d(dtype, (void*)in, (void*)Wt, (void*)out,
                           (float*)scale, (float*)bias, (void*)residual,
                           (void*)zero_page, Nb, H, W, C, Cout, KH, KW, sh, sw,
                           ph, pw, epi, as_stream(stream), tile,
                           test_scratch(conv_scratch_bytes(
                               Nb, H, W, C, Cout, KH, KW, sh, sw, ph, pw)),
-                          res_scale);
+                          res_scale, staging);
             if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
           },
           py::arg("dtype"), py::arg("in"), py::arg("Wt"), py::arg("out"),
@@ -401,7 +402,8 @@ PYBIND11_MODULE(_C, m) {
           py::arg("KH") = 1, py::arg("KW") = 1, py::arg("sh") = 1,
           py::arg("sw") = 1, py::arg("ph") = 0, py::arg("pw") = 0,
           py::arg("epi") = 0, py::arg("stream") = 0, py::arg("sync") = true,
-          py::arg("tile") = 0, py::arg("res_scale") = 1.0f);
+          py::arg("tile") = 0, py::arg("res_scale") = 1.0f,
+          py::arg("staging") = 0);
   ops.def("bottleneck_tail",
           [](int dtype, uintptr_t in, uintptr_t W1, uintptr_t W2,
              uintptr_t out, uintptr_t s1, uintptr_t b1, uintptr_t s2,

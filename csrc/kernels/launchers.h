@@ -19,7 +19,8 @@ void launch_conv2d(int dtype, const void* in, const void* Wt, void* out,
                    const void* zero_page, int Nb, int H, int W, int C,
                    int Cout, int KH, int KW, int sh, int sw, int ph, int pw,
                    int epi, hipStream_t stream, int tile = 0,
-                   void* scratch = nullptr, float res_scale = 1.0f);
+                   void* scratch = nullptr, float res_scale = 1.0f,
+                   int staging = 0);  // 0 = auto, 1 = force the general path
 size_t conv_scratch_bytes(int Nb, int H, int W, int C, int Cout, int KH,
                           int KW, int sh, int sw, int ph, int pw);
 

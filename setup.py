@@ -20,6 +20,10 @@ SOURCES = [
     "csrc/kernels/gemm_mx.hip",
     "csrc/kernels/decode.hip",
     "csrc/kernels/conv.hip",
+    "csrc/kernels/conv_f16.hip",
+    "csrc/kernels/conv_bf16.hip",
+    "csrc/kernels/conv_i8.hip",
+    "csrc/kernels/conv_fp8.hip",
     "csrc/kernels/splitk.hip",
     "csrc/kernels/pool.hip",
     "csrc/kernels/normalize.hip",
@@ -37,6 +41,7 @@ SOURCES = [
 HEADERS = [
     "csrc/common.h",
     "csrc/kernels/gemm_common.h",
+    "csrc/kernels/conv_igemm.h",
     "csrc/kernels/mx_common.h",
     "csrc/kernels/launchers.h",
     "csrc/kernels/sampling_common.h",

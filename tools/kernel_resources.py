@@ -9,7 +9,9 @@ args = sys.argv[1:]
 detail = None
 if args[:1] == ["--detail"]:
     detail, args = args[1], args[2:]
-srcs = args or ["csrc/kernels/conv.hip", "csrc/kernels/gemm.hip",
+srcs = args or ["csrc/kernels/conv.hip", "csrc/kernels/conv_f16.hip",
+                "csrc/kernels/conv_bf16.hip", "csrc/kernels/conv_i8.hip",
+                "csrc/kernels/conv_fp8.hip", "csrc/kernels/gemm.hip",
                 "csrc/kernels/attention.hip", "csrc/kernels/normalize.hip"]
 
 out = []
