@@ -686,26 +686,31 @@ PYBIND11_MODULE(_C, m) {
           [](uintptr_t qkv, uintptr_t kc, uintptr_t vc, int B, int H,
              int rows, int smax, uintptr_t pos, uintptr_t table,
              int max_pages, uintptr_t stream, bool sync, int D,
-             int kv_heads) {
+             int kv_heads, uintptr_t kscale, uintptr_t vscale,
+             int kv_format) {
             launch_kv_append((void*)qkv, (void*)kc, (void*)vc, (void*)pos,
                              (void*)table, max_pages, B, H, rows, smax,
-                             as_stream(stream), D, kv_heads);
+                             as_stream(stream), D, kv_heads, (void*)kscale,
+                             (void*)vscale, kv_format);
             if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
           },
           py::arg("qkv"), py::arg("kcache"), py::arg("vcache"), py::arg("B"),
           py::arg("H"), py::arg("rows"), py::arg("smax"), py::arg("pos") = 0,
           py::arg("table") = 0, py::arg("max_pages") = 0,
           py::arg("stream") = 0, py::arg("sync") = true, py::arg("D") = 64,
-          py::arg("kv_heads") = 0);
+          py::arg("kv_heads") = 0, py::arg("kscale") = 0,
+          py::arg("vscale") = 0, py::arg("kv_format") = 0);
   ops.def("decode_attention",
           [](uintptr_t qkv, uintptr_t kc, uintptr_t vc, uintptr_t out,
              uintptr_t pos, int B, int H, int rows, int smax, float scale,
              uintptr_t table, int max_pages, uintptr_t stream, bool sync,
-             int D, int kv_heads) {
+             int D, int kv_heads, uintptr_t kscale, uintptr_t vscale,
+             int kv_format) {
             launch_decode_attention((void*)qkv, (void*)kc, (void*)vc,
                                     (void*)out, (void*)pos, (void*)table,
                                     max_pages, B, H, rows, smax, scale,
-                                    as_stream(stream), D, kv_heads);
+                                    as_stream(stream), D, kv_heads,
+                                    (void*)kscale, (void*)vscale, kv_format);
             if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
           },
           py::arg("qkv"), py::arg("kcache"), py::arg("vcache"),
@@ -713,7 +718,8 @@ PYBIND11_MODULE(_C, m) {
           py::arg("rows"), py::arg("smax"), py::arg("scale"),
           py::arg("table") = 0, py::arg("max_pages") = 0,
           py::arg("stream") = 0, py::arg("sync") = true, py::arg("D") = 64,
-          py::arg("kv_heads") = 0);
+          py::arg("kv_heads") = 0, py::arg("kscale") = 0,
+          py::arg("vscale") = 0, py::arg("kv_format") = 0);
   ops.def("decode_embed",
           [](uintptr_t ids, uintptr_t tok, uintptr_t pe, uintptr_t out,
              uintptr_t pos, int B, int rows, int smax, int hidden,

@@ -38,7 +38,14 @@
 //     it: the host maps every page below pos[b] + rows before launch.
 //   smax is the session's position bound for both layouts, NOT
 //   max_pages*64: a shared pool may be larger than one session's window.
+//
+// A third, orthogonal axis is the cache ELEMENT format (Fp16Cache /
+// Mx8Cache below): fp16 rows, or MXFP8 rows — D e4m3 code bytes plus D/32
+// e8m0 scale bytes in a separate buffer. kv_append quantises, attention
+// dequantises in registers; the layouts, the bounds rule and the work
+// decomposition are the same for both.
 #include "gemm_common.h"
+#include "mx_common.h"
 
 namespace trtlab {
 
@@ -71,14 +78,38 @@ struct PagedKV {
   }
 };
 
+// Cache element format. Fp16Cache: the row is D fp16 values. Mx8Cache
+// (MXFP8): the row is D e4m3 bytes in the cache buffer (same shape as the
+// fp16 cache, 1-byte elements) plus D/32 e8m0 scale bytes, one per 32
+// consecutive elements, in kscale / vscale. Row offsets are multiples of
+// D, so the scale offset of a row is row / 32 for either layout and the
+// layout policies need no second addressing rule. The quantisation rule
+// is mx_common.h's (the one every MX producer shares): e = floor(log2
+// amax) - 8, codes saturate to +-448 and round to nearest even, scale
+// byte e + 127; an all-zero block stores byte 127.
+struct Fp16Cache {
+  using elem = _Float16;
+  static constexpr bool kMx = false;
+};
+struct Mx8Cache {
+  using elem = unsigned char;
+  static constexpr bool kMx = true;
+  unsigned char* kscale;
+  unsigned char* vscale;
+};
+
 // Scatter K/V head rows from the fused qkv projection output (qkv
 // [B*rows, (Hq + 2*Hkv)*D]) into the cache at position
 // (pos ? pos[b] : 0) + q. One block per (b, kv head, q); H is Hkv.
-template <class KV>
+// Mx8Cache (D = 64 or 128, launcher-checked): lane d owns element d (and
+// d + 64), its 32-element block is the 32-lane half of the wave it sits
+// in, so the block amax is five xor-shuffles; the lane with d % 32 == 0
+// stores the block's scale byte.
+template <class KV, class EF>
 __global__ __launch_bounds__(64) void kv_append_kernel(
-    const _Float16* __restrict__ qkv, _Float16* __restrict__ kcache,
-    _Float16* __restrict__ vcache, const int* __restrict__ pos, KV kv, int H,
-    int Hq, int rows, int smax, int D) {
+    const _Float16* __restrict__ qkv, typename EF::elem* __restrict__ kcache,
+    typename EF::elem* __restrict__ vcache, const int* __restrict__ pos,
+    KV kv, EF ef, int H, int Hq, int rows, int smax, int D) {
   int q = blockIdx.x % rows;
   int bh = blockIdx.x / rows;
   int b = bh / H, h = bh % H;
@@ -93,10 +124,45 @@ __global__ __launch_bounds__(64) void kv_append_kernel(
   if (dst < 0) return;  // unmapped page (host error) — fail soft, not wild
   int khid = H * D;
   int64_t src = ((int64_t)b * rows + q) * (Hq + 2 * H) * D + Hq * D + h * D;
-  for (int d = threadIdx.x; d < D; d += 64) {
-    kcache[dst + d] = qkv[src + d];
-    vcache[dst + d] = qkv[src + khid + d];
+  if constexpr (EF::kMx) {
+    // D is a multiple of 64: every lane runs the same trip count, so the
+    // shuffles below are wave-uniform.
+    for (int d = threadIdx.x; d < D; d += 64) {
+      float k = (float)qkv[src + d];
+      float v = (float)qkv[src + khid + d];
+      float ka = fabsf(k), va = fabsf(v);
+#pragma unroll
+      for (int off = 16; off; off >>= 1) {
+        ka = fmaxf(ka, __shfl_xor(ka, off, 64));
+        va = fmaxf(va, __shfl_xor(va, off, 64));
+      }
+      int ke = mx_block_exponent(ka, 8);
+      int ve = mx_block_exponent(va, 8);
+      kcache[dst + d] = mx_encode_e4m3(k * exp2f((float)-ke));
+      vcache[dst + d] = mx_encode_e4m3(v * exp2f((float)-ve));
+      if ((d & 31) == 0) {
+        ef.kscale[(dst + d) >> 5] = (unsigned char)(ke + 127);
+        ef.vscale[(dst + d) >> 5] = (unsigned char)(ve + 127);
+      }
+    }
+  } else {
+    for (int d = threadIdx.x; d < D; d += 64) {
+      kcache[dst + d] = qkv[src + d];
+      vcache[dst + d] = qkv[src + khid + d];
+    }
   }
+}
+
+// kv_format of the launchers: 0 fp16, 1 mxfp8 (needs both scale buffers).
+static bool kv_format_is_mx(const char* op, int kv_format, const void* kscale,
+                            const void* vscale) {
+  if (kv_format != 0 && kv_format != 1)
+    throw std::runtime_error(std::string(op) + ": unknown kv_format " +
+                             std::to_string(kv_format));
+  if (kv_format == 1 && (!kscale || !vscale))
+    throw std::runtime_error(std::string(op) +
+                             ": mxfp8 cache needs kscale and vscale");
+  return kv_format == 1;
 }
 
 // Hq query heads over Hkv kv heads: kv_heads = 0 means Hkv = Hq (MHA).
@@ -111,17 +177,26 @@ static int gqa_kv_heads(const char* op, int H, int kv_heads) {
 void launch_kv_append(const void* qkv, void* kcache, void* vcache,
                       const void* pos, const void* table, int max_pages,
                       int B, int H, int rows, int smax, hipStream_t stream,
-                      int D, int kv_heads) {
+                      int D, int kv_heads, void* kscale, void* vscale,
+                      int kv_format) {
   if (rows < 1) throw std::runtime_error("kv_append: rows < 1");
   int Hkv = gqa_kv_heads("kv_append", H, kv_heads);
-  auto L = [&](auto kv) {
-    hipLaunchKernelGGL(kv_append_kernel<decltype(kv)>, dim3(B * Hkv * rows),
-                       dim3(64), 0, stream, (const _Float16*)qkv,
-                       (_Float16*)kcache, (_Float16*)vcache, (const int*)pos,
-                       kv, Hkv, H, rows, smax, D);
+  bool mx = kv_format_is_mx("kv_append", kv_format, kscale, vscale);
+  if (mx && D != 64 && D != 128)
+    throw std::runtime_error("kv_append: mxfp8 head_dim must be 64 or 128");
+  auto L = [&](auto kv, auto ef) {
+    using E = typename decltype(ef)::elem;
+    hipLaunchKernelGGL((kv_append_kernel<decltype(kv), decltype(ef)>),
+                       dim3(B * Hkv * rows), dim3(64), 0, stream,
+                       (const _Float16*)qkv, (E*)kcache, (E*)vcache,
+                       (const int*)pos, kv, ef, Hkv, H, rows, smax, D);
   };
-  if (table) L(PagedKV{(const int*)table, max_pages});
-  else L(DenseKV{smax});
+  auto LE = [&](auto kv) {
+    if (mx) L(kv, Mx8Cache{(unsigned char*)kscale, (unsigned char*)vscale});
+    else L(kv, Fp16Cache{});
+  };
+  if (table) LE(PagedKV{(const int*)table, max_pages});
+  else LE(DenseKV{smax});
 }
 
 // Single-query attention against the cache: query row (b, q) attends keys
@@ -142,11 +217,20 @@ void launch_kv_append(const void* qkv, void* kcache, void* vcache,
 // G = 1 is the MHA kernel: same grid, same 16 KiB of LDS, same
 // arithmetic order. p_s is G * 16 KiB of static LDS (128 KiB at G = 8,
 // within the 160 KiB a gfx950 workgroup may declare).
-template <int D, int G, class KV>  // head_dim 64 or 128; group 1,2,4,8
+//
+// Mx8Cache: the lane's K row is D code bytes (16-byte loads, half of
+// fp16's) and D/32 scale bytes (one 2- or 4-byte load). Codes go through
+// the hardware fp8 -> f32 convert; each 32-element block's partial dot
+// product is scaled by 2^(byte - 127) with ldexp, which is exact, so the
+// score equals the one computed on the dequantised row with block-wise
+// accumulation. PV: lane d converts its V code byte and applies its
+// block's scale the same way. Everything from the softmax on is shared.
+template <int D, int G, class KV, class EF>  // D 64|128; G 1,2,4,8
 __global__ __launch_bounds__(64 * G) void decode_attention_kernel(
-    const _Float16* __restrict__ qkv, const _Float16* __restrict__ kcache,
-    const _Float16* __restrict__ vcache, _Float16* __restrict__ out,
-    const int* __restrict__ pos, KV kv, int H, int rows, int smax,
+    const _Float16* __restrict__ qkv,
+    const typename EF::elem* __restrict__ kcache,
+    const typename EF::elem* __restrict__ vcache, _Float16* __restrict__ out,
+    const int* __restrict__ pos, KV kv, EF ef, int H, int rows, int smax,
     float scale) {
   __shared__ float p_all[G * 4096];
   int q = blockIdx.x % rows;
@@ -176,14 +260,41 @@ __global__ __launch_bounds__(64 * G) void decode_attention_kernel(
   // scores for this lane's keys
   float m = -3.0e38f;
   for (int t = lane; t < n; t += 64) {
-    const _Float16* krow = kcache + kv.row(b, hk, H, D, t);
     float s = 0.f;
+    if constexpr (EF::kMx) {
+      int64_t r = kv.row(b, hk, H, D, t);
+      const unsigned char* krow = kcache + r;
+      using scales_t =
+          std::conditional_t<D == 128, unsigned int, unsigned short>;
+      unsigned int sb = *(const scales_t*)(ef.kscale + (r >> 5));
 #pragma unroll
-    for (int c = 0; c < D / 8; ++c) {
-      half8v v = *(const half8v*)(krow + c * 8);
+      for (int blk = 0; blk < D / 32; ++blk) {
+        float bs = 0.f;
 #pragma unroll
-      for (int j = 0; j < 8; ++j)
-        s += (float)qv[c * 8 + j] * (float)((const _Float16*)&v)[j];
+        for (int c = 0; c < 2; ++c) {
+          i32x4 w = *(const i32x4*)(krow + blk * 32 + c * 16);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(w[j], false);
+            auto hi = __builtin_amdgcn_cvt_pk_f32_fp8(w[j], true);
+            const _Float16* qe = qv + blk * 32 + c * 16 + j * 4;
+            bs += (float)qe[0] * lo[0];
+            bs += (float)qe[1] * lo[1];
+            bs += (float)qe[2] * hi[0];
+            bs += (float)qe[3] * hi[1];
+          }
+        }
+        s += ldexpf(bs, (int)((sb >> (8 * blk)) & 255u) - 127);
+      }
+    } else {
+      const _Float16* krow = kcache + kv.row(b, hk, H, D, t);
+#pragma unroll
+      for (int c = 0; c < D / 8; ++c) {
+        half8v v = *(const half8v*)(krow + c * 8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          s += (float)qv[c * 8 + j] * (float)((const _Float16*)&v)[j];
+      }
     }
     s *= scale;
     p_s[t] = s;
@@ -207,11 +318,23 @@ __global__ __launch_bounds__(64 * G) void decode_attention_kernel(
 #pragma unroll
   for (int j = 0; j < D / 64; ++j) acc[j] = 0.f;
   for (int t = 0; t < n; ++t) {
-    const _Float16* vrow = vcache + kv.row(b, hk, H, D, t);
     float p = p_s[t];
+    if constexpr (EF::kMx) {
+      int64_t r = kv.row(b, hk, H, D, t);
+      const unsigned char* vrow = vcache + r;
+      const unsigned char* srow = ef.vscale + (r >> 5);
 #pragma unroll
-    for (int j = 0; j < D / 64; ++j)
-      acc[j] += p * (float)vrow[j * 64 + lane];
+      for (int j = 0; j < D / 64; ++j) {
+        int d = j * 64 + lane;
+        float v = __builtin_amdgcn_cvt_f32_fp8((int)vrow[d], 0);
+        acc[j] += p * ldexpf(v, (int)srow[d >> 5] - 127);
+      }
+    } else {
+      const _Float16* vrow = vcache + kv.row(b, hk, H, D, t);
+#pragma unroll
+      for (int j = 0; j < D / 64; ++j)
+        acc[j] += p * (float)vrow[j * 64 + lane];
+    }
   }
 #pragma unroll
   for (int j = 0; j < D / 64; ++j)
@@ -223,7 +346,9 @@ void launch_decode_attention(const void* qkv, const void* kcache,
                              const void* vcache, void* out, const void* pos,
                              const void* table, int max_pages, int B, int H,
                              int rows, int smax, float scale,
-                             hipStream_t stream, int D, int kv_heads) {
+                             hipStream_t stream, int D, int kv_heads,
+                             const void* kscale, const void* vscale,
+                             int kv_format) {
   if (smax > 4096)
     throw std::runtime_error("decode_attention: smax > 4096 unsupported");
   if (D != 64 && D != 128)
@@ -234,20 +359,28 @@ void launch_decode_attention(const void* qkv, const void* kcache,
   if (G != 1 && G != 2 && G != 4 && G != 8)
     throw std::runtime_error(
         "decode_attention: heads / kv_heads must be 1, 2, 4 or 8");
-  auto L = [&](auto d_c, auto g_c, auto kv) {
+  bool mx = kv_format_is_mx("decode_attention", kv_format, kscale, vscale);
+  auto L = [&](auto d_c, auto g_c, auto kv, auto ef) {
+    using E = typename decltype(ef)::elem;
     hipLaunchKernelGGL(
         (decode_attention_kernel<decltype(d_c)::value, decltype(g_c)::value,
-                                 decltype(kv)>),
+                                 decltype(kv), decltype(ef)>),
         dim3(B * Hkv * rows), dim3(64 * decltype(g_c)::value), 0, stream,
-        (const _Float16*)qkv, (const _Float16*)kcache,
-        (const _Float16*)vcache, (_Float16*)out, (const int*)pos, kv, Hkv,
-        rows, smax, scale);
+        (const _Float16*)qkv, (const E*)kcache, (const E*)vcache,
+        (_Float16*)out, (const int*)pos, kv, ef, Hkv, rows, smax, scale);
+  };
+  auto LE = [&](auto d_c, auto g_c, auto kv) {
+    if (mx)
+      L(d_c, g_c, kv,
+        Mx8Cache{(unsigned char*)kscale, (unsigned char*)vscale});
+    else
+      L(d_c, g_c, kv, Fp16Cache{});
   };
   auto LG = [&](auto d_c, auto kv) {
-    if (G == 1) L(d_c, std::integral_constant<int, 1>{}, kv);
-    else if (G == 2) L(d_c, std::integral_constant<int, 2>{}, kv);
-    else if (G == 4) L(d_c, std::integral_constant<int, 4>{}, kv);
-    else L(d_c, std::integral_constant<int, 8>{}, kv);
+    if (G == 1) LE(d_c, std::integral_constant<int, 1>{}, kv);
+    else if (G == 2) LE(d_c, std::integral_constant<int, 2>{}, kv);
+    else if (G == 4) LE(d_c, std::integral_constant<int, 4>{}, kv);
+    else LE(d_c, std::integral_constant<int, 8>{}, kv);
   };
   using D64 = std::integral_constant<int, 64>;
   using D128 = std::integral_constant<int, 128>;

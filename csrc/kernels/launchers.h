@@ -152,17 +152,21 @@ void launch_quantize_mxfp8(const void* x, void* codes, void* scales,
 // rows = rows per slot (1 step, K verify chunk, P prefill range); table
 // null = dense [B][H][smax][D] caches, else paged pools through the
 // block table [B][max_pages]. pos may be null for kv_append only (base
-// position 0, no idle slots).
+// position 0, no idle slots). kv_format 0 = fp16 caches; 1 = MXFP8: the
+// caches hold e4m3 bytes (same shape) and kscale / vscale hold one e8m0
+// byte per 32 elements at offset row / 32 (D 64 or 128).
 void launch_kv_append(const void* qkv, void* kcache, void* vcache,
                       const void* pos, const void* table, int max_pages,
                       int B, int H, int rows, int smax, hipStream_t stream,
-                      int D = 64, int kv_heads = 0);
+                      int D = 64, int kv_heads = 0, void* kscale = nullptr,
+                      void* vscale = nullptr, int kv_format = 0);
 void launch_decode_attention(const void* qkv, const void* kcache,
                              const void* vcache, void* out, const void* pos,
                              const void* table, int max_pages, int B, int H,
                              int rows, int smax, float scale,
                              hipStream_t stream, int D = 64,
-                             int kv_heads = 0);
+                             int kv_heads = 0, const void* kscale = nullptr,
+                             const void* vscale = nullptr, int kv_format = 0);
 void launch_decode_embed(const void* ids, const void* tok, const void* posemb,
                          void* out, const void* pos, int B, int rows,
                          int smax, int hidden, hipStream_t stream);

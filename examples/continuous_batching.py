@@ -26,6 +26,9 @@ def main():
     ap.add_argument("--layers", type=int, default=12)
     ap.add_argument("--max-new", type=int, default=48)
     ap.add_argument("--paged", action="store_true", default=True)
+    ap.add_argument("--kv-dtype", choices=("fp16", "mxfp8"), default="fp16",
+                    help="KV cache element format: mxfp8 stores e4m3 codes "
+                         "+ per-32 e8m0 scales (33/64 of the fp16 bytes)")
     args = ap.parse_args()
 
     from trtlab_amd.engine.decode import DecodeSession
@@ -35,7 +38,7 @@ def main():
     g = build_gpt2(batch=1, seq=512, layers=args.layers, seed=0,
                    embeddings=True)
     sess = DecodeSession(g, batch=args.batch, smax=512, capture=True,
-                         lm_head=True, paged=True)
+                         lm_head=True, paged=True, kv_dtype=args.kv_dtype)
     pool = sess.kv_pool
 
     # request queue: each request = (prompt token, length to generate)

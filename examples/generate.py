@@ -35,6 +35,9 @@ def main():
                          "--draft-layers layers proposing K tokens/round "
                          "(output provably identical to plain greedy)")
     ap.add_argument("--draft-layers", type=int, default=2)
+    ap.add_argument("--kv-dtype", choices=("fp16", "mxfp8"), default="fp16",
+                    help="KV cache element format: mxfp8 stores e4m3 codes "
+                         "+ per-32 e8m0 scales (33/64 of the fp16 bytes)")
     args = ap.parse_args()
 
     def build(layers):
@@ -48,7 +51,10 @@ def main():
 
     g = build(args.layers)
     vocab = 32000 if args.arch == "llama" else 50257
-    sess = DecodeSession(g, batch=args.batch, smax=1024, lm_head=True)
+    sess = DecodeSession(g, batch=args.batch, smax=1024, lm_head=True,
+                         kv_dtype=args.kv_dtype)
+    print(f"KV cache: {args.kv_dtype}, "
+          f"{sess.kv_cache_bytes / 2**20:.0f} MiB")
 
     rng = np.random.RandomState(0)
     prompt = rng.randint(1, vocab,
@@ -68,7 +74,8 @@ def main():
                               capture=True, lm_head=True)
         draft.prefill(prompt)
         target = DecodeSession(g, batch=args.batch, smax=1024,
-                               capture=True, lm_head=True)
+                               capture=True, lm_head=True,
+                               kv_dtype=args.kv_dtype)
         target.prefill(prompt)
         sd = SpeculativeDecoder(target, draft, k=args.speculative)
         t0 = time.perf_counter()

@@ -38,12 +38,15 @@ def serve(args):
         g = build_gpt2(batch=args.batch, seq=args.smax,
                        hidden=args.hidden or 768, layers=args.layers,
                        seed=0, embeddings=True)
-    sess = DecodeSession(g, batch=args.batch, smax=args.smax, lm_head=True)
+    sess = DecodeSession(g, batch=args.batch, smax=args.smax, lm_head=True,
+                         kv_dtype=args.kv_dtype)
     svc = GenerationService(sess, device_truncation=args.device_sampling)
     srv = Server(f"0.0.0.0:{args.port}")
     srv.register_service(svc.service)
     srv.async_start()
-    print(f"generation server ({args.arch}, batch {args.batch}) "
+    print(f"generation server ({args.arch}, batch {args.batch}, "
+          f"{args.kv_dtype} KV cache "
+          f"{sess.kv_cache_bytes / 2**20:.0f} MiB) "
           f"on :{srv.port}; ctrl-c to stop", flush=True)
     try:
         while True:
@@ -87,6 +90,9 @@ def main():
     ap.add_argument("--layers", type=int, default=8)
     ap.add_argument("--hidden", type=int, default=0)
     ap.add_argument("--smax", type=int, default=1024)
+    ap.add_argument("--kv-dtype", choices=("fp16", "mxfp8"), default="fp16",
+                    help="KV cache element format: mxfp8 stores e4m3 codes "
+                         "+ per-32 e8m0 scales (33/64 of the fp16 bytes)")
     ap.add_argument("--port", type=int, default=50055)
     ap.add_argument("--prompt", type=int, nargs="*", default=[11, 42, 7])
     ap.add_argument("--new-tokens", type=int, default=32)

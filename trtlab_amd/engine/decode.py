@@ -29,12 +29,34 @@ carrying `kv_heads`) run natively: the qkv projection is
 (heads + 2*kv_heads)*head_dim wide, the dense caches are
 [B][kv_heads][smax][head_dim] and paged pools hold kv_heads heads per
 position, so KV memory is heads/kv_heads x smaller than for MHA.
+
+`kv_dtype="mxfp8"` (sessions and pools) stores K/V as MXFP8: e4m3 code
+bytes in caches of the fp16 shape plus one e8m0 scale byte per 32
+elements in separate `kscale` / `vscale` buffers — 33/64 of the fp16
+bytes for any model, no calibration. kv_append quantises, the decode
+attention dequantises in registers (csrc/kernels/decode.hip, element
+format policy); `_kv()` is the only place that knows.
 """
 from __future__ import annotations
 
 from typing import Dict, List, Optional
 
 import numpy as np
+
+KV_DTYPES = ("fp16", "mxfp8")
+_MX_BLOCK = 32  # elements per e8m0 scale byte
+
+
+def kv_row_bytes(head_dim: int, kv_dtype: str = "fp16") -> int:
+    """Bytes one (slot, kv head, position) row of K (or of V) occupies:
+    fp16 2*head_dim; mxfp8 head_dim code bytes + head_dim/32 scale bytes."""
+    if kv_dtype == "fp16":
+        return 2 * head_dim
+    if kv_dtype == "mxfp8":
+        if head_dim % _MX_BLOCK:
+            raise ValueError("mxfp8 KV rows need head_dim % 32 == 0")
+        return head_dim + head_dim // _MX_BLOCK
+    raise ValueError(f"unknown kv_dtype {kv_dtype!r} (fp16 | mxfp8)")
 
 
 
@@ -52,11 +74,16 @@ class PagedKVPool:
 
     def __init__(self, layers: int, heads: int, batch: int,
                  num_pages: int, max_pages_per_slot: int,
-                 device: int = 0, head_dim: int = 64):
+                 device: int = 0, head_dim: int = 64,
+                 kv_dtype: str = "fp16"):
+        """kv_dtype="mxfp8": the pools hold e4m3 bytes (same shape, u8)
+        and `kscales` / `vscales` hold the per-32-element e8m0 bytes,
+        [page][64][heads][head_dim/32] u8 per layer."""
         import torch
 
         from trtlab_amd import native
 
+        kv_row_bytes(head_dim, kv_dtype)  # validates kv_dtype
         self._C = native()
         self._torch = torch
         torch.cuda.set_device(device)
@@ -66,10 +93,19 @@ class PagedKVPool:
         self.num_pages = num_pages
         self.max_pages = max_pages_per_slot
         self.head_dim = head_dim
+        self.kv_dtype = kv_dtype
+        mx = kv_dtype == "mxfp8"
         self.kpools = [torch.zeros(num_pages, 64, heads, head_dim,
-                                   dtype=torch.half, device="cuda")
+                                   dtype=torch.uint8 if mx else torch.half,
+                                   device="cuda")
                        for _ in range(layers)]
         self.vpools = [torch.zeros_like(k) for k in self.kpools]
+        self.kscales = [torch.zeros(num_pages, 64, heads,
+                                    head_dim // _MX_BLOCK,
+                                    dtype=torch.uint8, device="cuda")
+                        for _ in range(layers)] if mx else None
+        self.vscales = ([torch.zeros_like(k) for k in self.kscales]
+                        if mx else None)
         self.table = torch.full((batch, max_pages_per_slot), -1,
                                 dtype=torch.int32, device="cuda")
         self._table_host = np.full((batch, max_pages_per_slot), -1,
@@ -119,8 +155,13 @@ class DecodeSession:
 
     def __init__(self, graph, batch: int, smax: int = 1024, device: int = 0,
                  capture: bool = True, lm_head: bool = False,
-                 fused: bool = False, paged=None):
-        """fused=True (needs batch <= 64): EXPERIMENTAL horizontal kernel
+                 fused: bool = False, paged=None, kv_dtype: str = "fp16"):
+        """kv_dtype: "fp16" (default) or "mxfp8" — K/V cached as e4m3
+        bytes plus per-32-element e8m0 scales (33/64 of the fp16 bytes;
+        see kv_row_bytes / kv_cache_bytes). A PagedKVPool passed as
+        `paged` must have been built with the same kv_dtype.
+
+        fused=True (needs batch <= 64): EXPERIMENTAL horizontal kernel
         fusion for the latency-bound step — LN / residual-add / embed
         prologues and KV-scatter / GeLU epilogues fold into the small-M
         GEMMs (csrc decode_gemm_fused), cutting ~8 kernels/layer to 5.
@@ -139,6 +180,12 @@ class DecodeSession:
         from trtlab_amd.engine.planner import (EPI_BIAS, EPI_BIAS_GELU,
                                                EPI_NONE)
 
+        if kv_dtype not in KV_DTYPES:
+            raise ValueError(f"unknown kv_dtype {kv_dtype!r} (fp16 | mxfp8)")
+        if fused and kv_dtype != "fp16":
+            raise ValueError("fused decode supports the fp16 KV cache only")
+        self.kv_dtype = kv_dtype
+        self._kv_format = KV_DTYPES.index(kv_dtype)  # the kernels' code
         self._C = native()
         self._torch = torch
         torch.cuda.set_device(device)
@@ -204,9 +251,17 @@ class DecodeSession:
                     n = nodes[f"l{li}_{key}"]
                     lay[key + "_w"] = dev16(n.attrs["weight"])
                     lay[key + "_b"] = dev32(n.attrs["bias"])
-            lay["kcache"] = torch.zeros(batch, self.kv_heads, smax, self.hd,
-                                        dtype=torch.half, device="cuda")
+            mx = kv_dtype == "mxfp8"
+            lay["kcache"] = torch.zeros(
+                batch, self.kv_heads, smax, self.hd,
+                dtype=torch.uint8 if mx else torch.half, device="cuda")
             lay["vcache"] = torch.zeros_like(lay["kcache"])
+            # mxfp8: one e8m0 byte per 32 elements, beside the codes
+            lay["kscale"] = torch.zeros(
+                batch, self.kv_heads, smax, self.hd // _MX_BLOCK,
+                dtype=torch.uint8, device="cuda") if mx else None
+            lay["vscale"] = (torch.zeros_like(lay["kscale"]) if mx
+                             else None)
             self.layers.append(lay)
             li += 1
         self.n_layers = li
@@ -265,14 +320,21 @@ class DecodeSession:
             self.kv_pool = paged if isinstance(paged, PagedKVPool) else \
                 PagedKVPool(self.n_layers, self.kv_heads, B,
                             num_pages=B * mp, max_pages_per_slot=mp,
-                            device=device, head_dim=self.hd)
+                            device=device, head_dim=self.hd,
+                            kv_dtype=kv_dtype)
             if self.kv_pool.layers != self.n_layers or \
                     self.kv_pool.heads != self.kv_heads or \
                     getattr(self.kv_pool, "head_dim", 64) != self.hd:
                 raise ValueError("pool layer/head mismatch")
+            if getattr(self.kv_pool, "kv_dtype", "fp16") != kv_dtype:
+                raise ValueError(
+                    f"pool kv_dtype {self.kv_pool.kv_dtype!r} != session "
+                    f"kv_dtype {kv_dtype!r}")
             for lay in self.layers:  # release the dense caches
                 lay["kcache"] = None
                 lay["vcache"] = None
+                lay["kscale"] = None
+                lay["vscale"] = None
         self.fused = bool(fused)
         if self.fused and self._nkv:
             raise ValueError("fused decode does not support grouped-query "
@@ -374,20 +436,40 @@ class DecodeSession:
             pool = self.kv_pool
             kc, vc = pool.kpools[li].data_ptr(), pool.vpools[li].data_ptr()
             table, mp = pool.table.data_ptr(), pool.max_pages
+            sc = (pool.kscales[li], pool.vscales[li]) \
+                if self._kv_format else None
         else:
             kc, vc = lay["kcache"].data_ptr(), lay["vcache"].data_ptr()
             table, mp = 0, 0
+            sc = (lay["kscale"], lay["vscale"]) if self._kv_format else None
+        # element format: fp16 (no scales) or mxfp8 codes + block scales
+        fmt = dict(kscale=sc[0].data_ptr(), vscale=sc[1].data_ptr(),
+                   kv_format=self._kv_format) if sc else {}
         ops.kv_append(qkv_ptr, kc, vc, self.batch, self.heads, rows,
                       self.smax, pos=self.pos.data_ptr() if att_ptr else 0,
                       table=table, max_pages=mp, stream=s, sync=False,
-                      D=self.hd, kv_heads=self._nkv)
+                      D=self.hd, kv_heads=self._nkv, **fmt)
         if att_ptr:
             scale = 1.0 / float(np.sqrt(float(self.hd)))
             ops.decode_attention(qkv_ptr, kc, vc, att_ptr,
                                  self.pos.data_ptr(), self.batch,
                                  self.heads, rows, self.smax, scale,
                                  table=table, max_pages=mp, stream=s,
-                                 sync=False, D=self.hd, kv_heads=self._nkv)
+                                 sync=False, D=self.hd, kv_heads=self._nkv,
+                                 **fmt)
+
+    @property
+    def kv_cache_bytes(self) -> int:
+        """Bytes of K/V storage behind this session: the dense caches
+        (2 * layers * batch * kv_heads * smax rows) or the whole paged
+        pool (2 * layers * num_pages * 64 * kv_heads rows), at
+        kv_row_bytes(head_dim, kv_dtype) per row."""
+        if self.kv_pool is not None:
+            rows = self.kv_pool.num_pages * 64 * self.kv_heads
+        else:
+            rows = self.batch * self.kv_heads * self.smax
+        return 2 * self.n_layers * rows * kv_row_bytes(self.hd,
+                                                       self.kv_dtype)
 
     def _enqueue_llama(self):
         """One LLaMA decode step (pos-relative, captured like the gpt2

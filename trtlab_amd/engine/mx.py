@@ -6,6 +6,12 @@ MFMA (mfma_scale_f32_16x16x128_f8f6f4) — gfx950's highest-throughput GEMM
 instruction, with no equivalent in the CUDA reference. The planner's
 DT_MX8 / DT_MX4 plans quantize weights with these codecs; activations are
 quantized on the device (tests/test_mx_kernels_gpu.py, tools/bench_mx.py).
+
+The MXFP8 KV cache (DecodeSession(kv_dtype="mxfp8")) stores every K/V head
+row as one [1, D] quantize_mxfp8 row; quantize_mxfp8 / dequantize_mxfp8 are
+its oracle (engine/reference.py kv_format="mxfp8"). One convention differs
+between host and device: an all-zero block stores scale byte 119 here and
+127 on the device (both dequantise to 0).
 """
 from __future__ import annotations
 

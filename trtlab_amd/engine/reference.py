@@ -45,10 +45,29 @@ def _epi(acc: torch.Tensor, epi: int, scale, bias, res) -> torch.Tensor:
     return v
 
 
-def run_reference(plan: EnginePlan, input_nhwc, return_all: bool = False):
+def _mx8_kv_roundtrip(x: torch.Tensor) -> torch.Tensor:
+    """[..., D] K or V head rows as an MXFP8 KV cache holds them: rounded
+    to fp16 (what the qkv projection stores), then quantize_mxfp8 /
+    dequantize_mxfp8 per head row."""
+    from trtlab_amd.engine.mx import dequantize_mxfp8, quantize_mxfp8
+
+    rows = x.half().float().reshape(-1, x.shape[-1]).numpy()
+    out = dequantize_mxfp8(*quantize_mxfp8(rows))
+    return torch.from_numpy(out).reshape(x.shape)
+
+
+def run_reference(plan: EnginePlan, input_nhwc, return_all: bool = False,
+                  kv_format=None):
     """Run the plan on CPU (fp32). input is the RAW (unpadded) primary
     input, or a {name: array} dict for multi-binding models. With
-    return_all=True, returns the dict of ALL tensors (debugging)."""
+    return_all=True, returns the dict of ALL tensors (debugging).
+
+    kv_format="mxfp8": every attention op reads K and V through the
+    MXFP8 KV-cache round trip (_mx8_kv_roundtrip). With a causal mask
+    that full-sequence pass is what a DecodeSession(kv_dtype="mxfp8")
+    computes step by step: each query attends dequantised cache rows."""
+    if kv_format not in (None, "fp16", "mxfp8"):
+        raise ValueError(f"run_reference: unknown kv_format {kv_format!r}")
     if isinstance(input_nhwc, dict):
         t: Dict[str, torch.Tensor] = {
             k: torch.from_numpy(np.ascontiguousarray(v)).float()
@@ -238,6 +257,8 @@ def run_reference(plan: EnginePlan, input_nhwc, return_all: bool = False):
                 q = qkv[:, :, 0].permute(0, 2, 1, 3)  # [B, NH, S, HD]
                 k = qkv[:, :, 1].permute(0, 2, 1, 3)
                 v = qkv[:, :, 2].permute(0, 2, 1, 3)
+            if kv_format == "mxfp8":
+                k, v = _mx8_kv_roundtrip(k), _mx8_kv_roundtrip(v)
             scores = q @ k.transpose(-1, -2) * d["att_scale"]
             if len(op.inputs) > 1:  # varlen: mask right-padded keys
                 lens = t[op.inputs[1]].long()
