@@ -765,17 +765,19 @@ PYBIND11_MODULE(_C, m) {
   ops.def("attention",
           [](int dtype, uintptr_t qkv, uintptr_t out, int B, int S, int H,
              int D, float scale, uintptr_t stream, bool sync, int causal,
-             uintptr_t seqlens, int kv_heads) {
+             uintptr_t seqlens, int kv_heads, int out_dtype,
+             float out_scale) {
             launch_attention(dtype, (void*)qkv, (void*)out, B, S, H, D, scale,
-                             as_stream(stream), -1, 1.0f, (void*)seqlens,
-                             causal, kv_heads);
+                             as_stream(stream), out_dtype, out_scale,
+                             (void*)seqlens, causal, kv_heads);
             if (sync) TRT_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
           },
           py::arg("dtype"), py::arg("qkv"), py::arg("out"), py::arg("B"),
           py::arg("S"), py::arg("H"), py::arg("D"), py::arg("scale"),
           py::arg("stream") = 0, py::arg("sync") = true,
           py::arg("causal") = 0, py::arg("seqlens") = 0,
-          py::arg("kv_heads") = 0);
+          py::arg("kv_heads") = 0, py::arg("out_dtype") = -1,
+          py::arg("out_scale") = 1.0f);
 
   // --------------------------------------------------------------- comm
   // Owned RCCL collective layer (no torch.distributed in the data path).

@@ -493,20 +493,21 @@ __global__ __launch_bounds__(256) void attention_kernel_d128(
   }
 }
 
-// Debug probe: each block writes its view of the launch parameters.
-__global__ void attention_probe_kernel(int* dbg, int B, int S, int H, int D) {
-  if (threadIdx.x == 0) {
-    int bh = blockIdx.x;
-    int* p = dbg + bh * 8;
-    p[0] = B; p[1] = S; p[2] = H; p[3] = D;
-    p[4] = (int)gridDim.x; p[5] = bh; p[6] = bh / H; p[7] = bh % H;
-  }
-}
-
-void launch_attention_probe(int* dbg, int B, int S, int H, int D,
-                            hipStream_t stream) {
-  hipLaunchKernelGGL(attention_probe_kernel, dim3(B * H), dim3(256), 0,
-                     stream, dbg, B, S, H, D);
+template <typename T, typename OT>
+static void launch_attention_typed(const void* qkv, void* out, int B, int S,
+                                   int H, int D, float scale, float out_scale,
+                                   const int* lens, int causal, int Hkv,
+                                   hipStream_t stream) {
+  dim3 grid(B * H * ((S + 63) / 64));  // 64-query-row blocks (+ tail)
+  dim3 block(256);
+  if (D == 128)
+    hipLaunchKernelGGL((attention_kernel_d128<T, OT>), grid, block, 0, stream,
+                       (const T*)qkv, (OT*)out, B, S, H, scale, out_scale,
+                       lens, causal, Hkv);
+  else
+    hipLaunchKernelGGL((attention_kernel<T, OT>), grid, block, 0, stream,
+                       (const T*)qkv, (OT*)out, B, S, H, D, scale, out_scale,
+                       lens, causal, Hkv);
 }
 
 void launch_attention(int dtype, const void* qkv, void* out, int B, int S,
@@ -520,43 +521,19 @@ void launch_attention(int dtype, const void* qkv, void* out, int B, int S,
     throw std::runtime_error(
         "attention: heads must be a multiple of kv_heads");
   if (S < 1) throw std::runtime_error("attention: S must be >= 1");
-  dim3 grid(B * H * ((S + 63) / 64));  // 64-query-row blocks (+ tail)
-  dim3 block(256);
   const int* lens = (const int*)seqlens;
-  if (D == 128) {
-    if (dtype == 0) {
-      if (out_dtype == 3)
-        hipLaunchKernelGGL((attention_kernel_d128<_Float16, __hip_fp8_e4m3>),
-                           grid, block, 0, stream, (const _Float16*)qkv,
-                           (__hip_fp8_e4m3*)out, B, S, H, scale, out_scale,
-                           lens, causal, Hkv);
-      else
-        hipLaunchKernelGGL((attention_kernel_d128<_Float16, _Float16>), grid,
-                           block, 0, stream, (const _Float16*)qkv,
-                           (_Float16*)out, B, S, H, scale, out_scale, lens,
-                           causal, Hkv);
-    } else {
-      hipLaunchKernelGGL((attention_kernel_d128<__bf16, __bf16>), grid, block,
-                         0, stream, (const __bf16*)qkv, (__bf16*)out, B, S, H,
-                         scale, out_scale, lens, causal, Hkv);
-    }
-    return;
-  }
-  if (dtype == 0) {
-    if (out_dtype == 3)  // fused fp8 output for the projection GEMM
-      hipLaunchKernelGGL((attention_kernel<_Float16, __hip_fp8_e4m3>), grid,
-                         block, 0, stream, (const _Float16*)qkv,
-                         (__hip_fp8_e4m3*)out, B, S, H, D, scale, out_scale,
-                         lens, causal, Hkv);
-    else
-      hipLaunchKernelGGL((attention_kernel<_Float16, _Float16>), grid, block,
-                         0, stream, (const _Float16*)qkv, (_Float16*)out, B,
-                         S, H, D, scale, out_scale, lens, causal, Hkv);
-  } else {
-    hipLaunchKernelGGL((attention_kernel<__bf16, __bf16>), grid, block, 0,
-                       stream, (const __bf16*)qkv, (__bf16*)out, B, S, H, D,
-                       scale, out_scale, lens, causal, Hkv);
-  }
+  if (dtype != 0)
+    launch_attention_typed<__bf16, __bf16>(qkv, out, B, S, H, D, scale,
+                                           out_scale, lens, causal, Hkv,
+                                           stream);
+  else if (out_dtype == 3)  // fused fp8 output for the projection GEMM
+    launch_attention_typed<_Float16, __hip_fp8_e4m3>(qkv, out, B, S, H, D,
+                                                     scale, out_scale, lens,
+                                                     causal, Hkv, stream);
+  else
+    launch_attention_typed<_Float16, _Float16>(qkv, out, B, S, H, D, scale,
+                                               out_scale, lens, causal, Hkv,
+                                               stream);
 }
 
 // ---- seqlens from right-padded token ids ----

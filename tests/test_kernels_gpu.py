@@ -231,6 +231,25 @@ def test_channel_pad(C):
     check(out, ref, rtol=1e-3, atol=1e-3)
 
 
+def _attention_ref(qkv, B, S, H, D, causal=0, lens=None):
+    """Plain torch fp32 attention over a fused qkv [B*S, 3*H*D] (column
+    blocks q|k|v): optional causal mask, optional per-sequence valid key
+    counts `lens` (keys >= lens[b] masked). Returns [B*S, H*D] fp32."""
+    q = qkv.float().reshape(B, S, 3, H, D)
+    scores = (q[:, :, 0].permute(0, 2, 1, 3) @
+              q[:, :, 1].permute(0, 2, 1, 3).transpose(-1, -2)) / (D ** 0.5)
+    if causal:
+        cm = torch.arange(S, device="cuda")[None, :] > \
+            torch.arange(S, device="cuda")[:, None]
+        scores = scores.masked_fill(cm[None, None], float("-inf"))
+    if lens is not None:
+        for b in range(B):
+            scores[b, :, :, lens[b]:] = float("-inf")
+    att = torch.softmax(scores, dim=-1)
+    return (att @ q[:, :, 2].permute(0, 2, 1, 3)).permute(
+        0, 2, 1, 3).reshape(B * S, H * D)
+
+
 def test_attention(C):
     B, S, H, D = 2, 128, 12, 64
     hid = H * D
@@ -239,12 +258,7 @@ def test_attention(C):
     torch.cuda.synchronize()
     C.ops.attention(0, qkv.data_ptr(), out.data_ptr(), B, S, H, D,
                     1.0 / (D ** 0.5))
-    q = qkv.float().reshape(B, S, 3, H, D)
-    att = torch.softmax(
-        (q[:, :, 0].permute(0, 2, 1, 3) @ q[:, :, 1].permute(0, 2, 1, 3).transpose(-1, -2))
-        / (D ** 0.5), dim=-1)
-    ref = (att @ q[:, :, 2].permute(0, 2, 1, 3)).permute(0, 2, 1, 3).reshape(B * S, hid)
-    check(out, ref)
+    check(out, _attention_ref(qkv, B, S, H, D))
 
 
 def test_gemm_bt_int8(C):
@@ -434,17 +448,7 @@ def test_attention_long_and_causal(C, S, causal, D):
     torch.cuda.synchronize()
     C.ops.attention(0, qkv.data_ptr(), out.data_ptr(), B, S, H, D,
                     1.0 / (D ** 0.5), causal=causal)
-    q = qkv.float().reshape(B, S, 3, H, D)
-    scores = (q[:, :, 0].permute(0, 2, 1, 3) @
-              q[:, :, 1].permute(0, 2, 1, 3).transpose(-1, -2)) / (D ** 0.5)
-    if causal:
-        cm = torch.arange(S, device="cuda")[None, :] > \
-            torch.arange(S, device="cuda")[:, None]
-        scores = scores.masked_fill(cm[None, None], float("-inf"))
-    att = torch.softmax(scores, dim=-1)
-    ref = (att @ q[:, :, 2].permute(0, 2, 1, 3)).permute(
-        0, 2, 1, 3).reshape(B * S, hid)
-    check(out, ref)
+    check(out, _attention_ref(qkv, B, S, H, D, causal=causal))
 
 
 @pytest.mark.parametrize("S,D", [(200, 64), (200, 128), (384, 128)])
@@ -459,19 +463,58 @@ def test_attention_varlen_odd_s(C, S, D):
     torch.cuda.synchronize()
     C.ops.attention(0, qkv.data_ptr(), out.data_ptr(), B, S, H, D,
                     1.0 / (D ** 0.5), seqlens=lens.data_ptr())
-    q = qkv.float().reshape(B, S, 3, H, D)
-    scores = (q[:, :, 0].permute(0, 2, 1, 3) @
-              q[:, :, 1].permute(0, 2, 1, 3).transpose(-1, -2)) / (D ** 0.5)
-    for b in range(B):
-        scores[b, :, :, lens[b]:] = float("-inf")
-    att = torch.softmax(scores, dim=-1)
-    ref = (att @ q[:, :, 2].permute(0, 2, 1, 3)).permute(
-        0, 2, 1, 3).reshape(B * S, hid)
+    ref = _attention_ref(qkv, B, S, H, D, lens=lens)
     # compare only valid query rows (padded rows are don't-care)
     valid = torch.zeros(B * S, dtype=torch.bool)
     for b in range(B):
         valid[b * S:b * S + int(lens[b])] = True
     check(out[valid.to(out.device)], ref[valid.to(ref.device)])
+
+
+@pytest.mark.parametrize("causal", [0, 1])
+@pytest.mark.parametrize("S", [77, 192])
+@pytest.mark.parametrize("D", [64, 128])
+def test_attention_bf16(C, D, S, causal):
+    """bf16 in / bf16 out, both head dims. S = 77 is one partial key tile
+    and a partial query block; S = 192 is a full 128-key tile plus a tail
+    at D = 64 and three 64-key tiles at D = 128."""
+    B, H = 2, 4
+    hid = H * D
+    g = torch.Generator(device="cuda").manual_seed(500 + S + causal + D)
+    qkv = torch.randn(B * S, 3 * hid, generator=g,
+                      device="cuda").bfloat16().contiguous()
+    out = torch.empty(B * S, hid, dtype=torch.bfloat16, device="cuda")
+    torch.cuda.synchronize()
+    C.ops.attention(1, qkv.data_ptr(), out.data_ptr(), B, S, H, D,
+                    1.0 / (D ** 0.5), causal=causal)
+    check(out, _attention_ref(qkv, B, S, H, D, causal=causal),
+          rtol=4e-2, atol=4e-2)
+
+
+@pytest.mark.parametrize("S,causal", [(77, 0), (192, 1)])
+@pytest.mark.parametrize("D", [64, 128])
+def test_attention_fp8_out(C, D, S, causal):
+    """fp16 in, fused e4m3 output of value * out_scale. out_scale = 8 is a
+    power of two (the scaling is exact) and outputs are convex combinations
+    of unit-normal V entries, so 8x stays far below the 448 clamp. Per
+    element tolerance: the fp16 attention tolerance (2e-2 + 2e-2 |ref|) plus
+    2**-4 |ref|, the half-step of e4m3's 3-bit mantissa under round-to-
+    nearest. The guard tail behind the output must stay untouched."""
+    B, H = 2, 4
+    hid = H * D
+    out_scale, guard = 8.0, 256
+    qkv = t16(B * S, 3 * hid, seed=700 + S + causal + D)
+    buf = torch.full((B * S * hid + guard,), 0xA5, dtype=torch.uint8,
+                     device="cuda")
+    torch.cuda.synchronize()
+    C.ops.attention(0, qkv.data_ptr(), buf.data_ptr(), B, S, H, D,
+                    1.0 / (D ** 0.5), causal=causal, out_dtype=3,
+                    out_scale=out_scale)
+    assert (buf[B * S * hid:] == 0xA5).all(), "guard tail overwritten"
+    out = buf[:B * S * hid].view(torch.float8_e4m3fn).float().reshape(
+        B * S, hid) / out_scale
+    check(out, _attention_ref(qkv, B, S, H, D, causal=causal),
+          rtol=2e-2 + 2 ** -4, atol=2e-2)
 
 
 def test_gemm_bt_tile256(C):
