@@ -4,11 +4,22 @@ Beyond-reference capability (the CUDA reference served static TensorRT
 engines only): a `DecodeSession` holds per-layer K/V caches resident in
 HBM and replays ONE hipGraph per generated token. All position dependence
 flows through a device-side counter (csrc/kernels/decode.hip), so the
-captured graph needs no re-instantiation between steps:
+captured graph needs no re-instantiation between steps.
 
-    embed(ids, pos) -> [per layer: ln1 -> qkv gemm -> kv_append ->
-    decode_attention -> proj gemm -> +res -> ln2 -> ff1+gelu -> ff2 ->
-    +res] -> ln_f -> advance_pos
+The transformer forward is written once, in `DecodeSession._forward`:
+
+    norm1 -> [per layer: qkv gemm -> rope (LLaMA) -> kv_append +
+    attention -> proj gemm -> +res, norm2 -> MLP -> +res, next norm1 |
+    final norm]
+
+recorded for a buffer set and one of three pass kinds: "step" (one row
+per slot at the device position), "chunk" (K rows per slot, speculative
+verification) and "prefill" (the whole padded prompt: append only, then
+full-sequence causal attention). The GPT-2 / LLaMA difference (LayerNorm
++ biased GEMMs + GELU vs RMSNorm + RoPE + SwiGLU) lives in that one
+function; the embedding in front and the lm head / argmax / advance_pos
+behind it belong to the pass (`_enqueue`, `_enqueue_chunk`, `prefill`).
+`_enqueue_fused` is the separate experimental fused-kernel step.
 
 Caveat: the raw-op GEMMs share the lazily-grown module-level scratch
 buffer (csrc/ext.cpp test_scratch); the captured graph bakes its address,
@@ -324,9 +335,9 @@ class DecodeSession:
                             kv_dtype=kv_dtype)
             if self.kv_pool.layers != self.n_layers or \
                     self.kv_pool.heads != self.kv_heads or \
-                    getattr(self.kv_pool, "head_dim", 64) != self.hd:
+                    self.kv_pool.head_dim != self.hd:
                 raise ValueError("pool layer/head mismatch")
-            if getattr(self.kv_pool, "kv_dtype", "fp16") != kv_dtype:
+            if self.kv_pool.kv_dtype != kv_dtype:
                 raise ValueError(
                     f"pool kv_dtype {self.kv_pool.kv_dtype!r} != session "
                     f"kv_dtype {kv_dtype!r}")
@@ -347,9 +358,16 @@ class DecodeSession:
             raise ValueError("fused decode supports head_dim 64 only")
         if self.fused and self.kv_pool is not None:
             raise ValueError("fused + paged not supported together yet")
+        self._scale = 1.0 / float(np.sqrt(float(self.hd)))  # attention
         self.stream = self._C.hip.stream_create()
         self._graph = 0
         self._steps = 0
+        # verify_chunk: buffers and captured graph per chunk size K
+        self._chunk_bufs_by_k: Dict[int, Dict] = {}
+        self._chunk_graphs: Dict[int, int] = {}
+        # sample_tokens: per-slot parameters on the device, made on first use
+        self._temps_dev = self._seeds_dev = None
+        self._topk_dev = self._topp_dev = None
 
     # ------------------------------------------------------------ plumbing
     def _enqueue_fused(self):
@@ -450,10 +468,9 @@ class DecodeSession:
                       table=table, max_pages=mp, stream=s, sync=False,
                       D=self.hd, kv_heads=self._nkv, **fmt)
         if att_ptr:
-            scale = 1.0 / float(np.sqrt(float(self.hd)))
             ops.decode_attention(qkv_ptr, kc, vc, att_ptr,
                                  self.pos.data_ptr(), self.batch,
-                                 self.heads, rows, self.smax, scale,
+                                 self.heads, rows, self.smax, self._scale,
                                  table=table, max_pages=mp, stream=s,
                                  sync=False, D=self.hd, kv_heads=self._nkv,
                                  **fmt)
@@ -471,137 +488,135 @@ class DecodeSession:
         return 2 * self.n_layers * rows * kv_row_bytes(self.hd,
                                                        self.kv_dtype)
 
-    def _enqueue_llama(self):
-        """One LLaMA decode step (pos-relative, captured like the gpt2
-        recipe): embed -> [per layer: rmsnorm -> qkv gemm -> rope(pos) ->
-        kv_append -> decode_attention -> proj -> add_rmsnorm(res fused) ->
-        gate/up gemms -> silu_mul -> down -> add_rmsnorm] -> rms_f ->
-        [lm head] -> advance_pos. No biases anywhere (LLaMA); RoPE reads
-        the device position counter directly (pos_dev[row], idle slots
-        skip), so the captured graph stays position-free."""
-        C, s = self._C, self.stream
-        B, Hd = self.batch, self.hidden
-        T4 = 0
-        ops = C.ops
-        ops.decode_embed(self.ids.data_ptr(), self.tok.data_ptr(),
-                         self.posemb.data_ptr(), self.h.data_ptr(),
-                         self.pos.data_ptr(), B, 1, self.smax, Hd, stream=s,
-                         sync=False)
-        ops.rmsnorm(0, self.h.data_ptr(),
-                    self.layers[0]["rms1_g"].data_ptr(), self.x.data_ptr(),
-                    B, Hd, eps=self.rms_eps, stream=s, sync=False)
+    def _forward(self, b: Dict, kind: str, rows: int) -> None:
+        """Record one transformer forward over batch*rows rows on the
+        session stream (no syncs — capturable).
+
+        b: the buffer roles `h` (residual stream, holds the embeddings on
+        entry), `x`, `qkv`, `att`, `x2`, `ff`, `ff2` (LLaMA only) and
+        `out`, where the final norm lands. `att` may alias `x`: `x` is
+        dead once the qkv GEMM has read it.
+        kind / rows per slot:
+          "step"    1   at the device position pos[b]
+          "chunk"   K   at pos[b] + row (chunk-strided RoPE)
+          "prefill" Pp  at position row (null pos): KV append only, then
+                        full-sequence causal attention
+        The step is kernel-COUNT bound (~4.6 us graph-replay floor per
+        kernel regardless of size - profiles/dec_kernel_stats), so every
+        residual add is fused into the following norm (sum_out updates
+        the residual stream in the same kernel)."""
+        ops, s = self._C.ops, self.stream
+        M, Hd, inter = self.batch * rows, self.hidden, self.inter
+        llama = self.arch == "llama"
+        prefill = kind == "prefill"
+        h, x, qkv, att, x2, ff, out = (
+            b[k].data_ptr() for k in ("h", "x", "qkv", "att", "x2", "ff",
+                                      "out"))
+
+        def gemm(a, w, c, N, K, bias=None, epi=self._epi_none):
+            ops.gemm_bt(0, a, w.data_ptr(), c,
+                        bias=bias.data_ptr() if bias is not None else 0,
+                        M=M, N=N, K=K, epi=epi, stream=s, sync=False)
+
+        def norm(src, g, beta, dst, res=0):
+            """dst = norm(src); with res: res += src first, same kernel."""
+            if llama and res:
+                ops.add_rmsnorm(0, src, res, g.data_ptr(), dst, sum_out=res,
+                                M=M, N=Hd, eps=self.rms_eps, stream=s,
+                                sync=False)
+            elif llama:
+                ops.rmsnorm(0, src, g.data_ptr(), dst, M, Hd,
+                            eps=self.rms_eps, stream=s, sync=False)
+            elif res:
+                ops.add_layernorm(0, src, res, g.data_ptr(),
+                                  beta.data_ptr(), dst, sum_out=res, M=M,
+                                  N=Hd, stream=s, sync=False)
+            else:
+                ops.layernorm(0, src, g.data_ptr(), beta.data_ptr(), dst, M,
+                              Hd, stream=s, sync=False)
+
+        def norm1(lay):
+            return ((lay["rms1_g"], None) if llama
+                    else (lay["ln1_g"], lay["ln1_b"]))
+
+        norm(h, *norm1(self.layers[0]), x)
         for li, lay in enumerate(self.layers):
-            ops.gemm_bt(0, self.x.data_ptr(), lay["qkv_w"].data_ptr(),
-                        self.qkv.data_ptr(), M=B, N=self.qkv_w, K=Hd,
-                        epi=self._epi_none, stream=s, sync=False, tile=T4)
-            ops.rope(0, self.qkv.data_ptr(), pos=self.pos.data_ptr(), M=B,
-                     S=self.smax, H=self.heads, D=self.hd, theta=self.theta,
-                     stream=s, sync=False, kv_heads=self._nkv)
-            self._kv(li, lay, self.qkv.data_ptr(), 1, self.att.data_ptr())
-            ops.gemm_bt(0, self.att.data_ptr(), lay["proj_w"].data_ptr(),
-                        self.x2.data_ptr(), M=B, N=Hd, K=Hd,
-                        epi=self._epi_none, stream=s, sync=False, tile=T4)
-            # h += proj; x = rms2(h)  (one kernel, sum_out = new residual)
-            ops.add_rmsnorm(0, self.x2.data_ptr(), self.h.data_ptr(),
-                            lay["rms2_g"].data_ptr(), self.x.data_ptr(),
-                            sum_out=self.h.data_ptr(), M=B, N=Hd,
-                            eps=self.rms_eps, stream=s, sync=False)
-            ops.gemm_bt(0, self.x.data_ptr(), lay["gate_w"].data_ptr(),
-                        self.ff.data_ptr(), M=B, N=self.inter, K=Hd,
-                        epi=self._epi_none, stream=s, sync=False, tile=T4)
-            ops.gemm_bt(0, self.x.data_ptr(), lay["up_w"].data_ptr(),
-                        self.ff2.data_ptr(), M=B, N=self.inter, K=Hd,
-                        epi=self._epi_none, stream=s, sync=False, tile=T4)
-            ops.silu_mul(0, self.ff.data_ptr(), self.ff2.data_ptr(),
-                         self.ff.data_ptr(), B * self.inter, stream=s,
-                         sync=False)
-            ops.gemm_bt(0, self.ff.data_ptr(), lay["down_w"].data_ptr(),
-                        self.x2.data_ptr(), M=B, N=Hd, K=self.inter,
-                        epi=self._epi_none, stream=s, sync=False, tile=T4)
-            nxt = (self.layers[li + 1] if li + 1 < self.n_layers else None)
-            gptr = (nxt["rms1_g"] if nxt else self.lnf_g).data_ptr()
-            dst = (self.x if nxt else self.out).data_ptr()
-            ops.add_rmsnorm(0, self.x2.data_ptr(), self.h.data_ptr(), gptr,
-                            dst, sum_out=self.h.data_ptr(), M=B, N=Hd,
-                            eps=self.rms_eps, stream=s, sync=False)
-        if self.logits is not None:
-            ops.gemm_bt(0, self.out.data_ptr(), self.tok.data_ptr(),
-                        self.logits.data_ptr(), M=B, N=self.vocab, K=Hd,
-                        epi=self._epi_none, stream=s, sync=False)
-            ops.argmax_rows(self.logits.data_ptr(), self.gids.data_ptr(),
-                            B, self.vocab, stream=s, sync=False)
-        ops.advance_pos(self.pos.data_ptr(), B, self.smax, stream=s,
-                        sync=False)
+            if llama:
+                gemm(x, lay["qkv_w"], qkv, self.qkv_w, Hd)
+                # rotates at pos[b] (+ row in a chunk); prefill: at
+                # row % rows (exact for rows < P; the padded tail is
+                # causal-masked / overwritten before it is read)
+                ops.rope(0, qkv, pos=0 if prefill else self.pos.data_ptr(),
+                         M=M, S=rows if prefill else self.smax,
+                         H=self.heads, D=self.hd, theta=self.theta,
+                         stream=s, sync=False,
+                         chunk=rows if kind == "chunk" else 0,
+                         kv_heads=self._nkv)
+            else:
+                gemm(x, lay["qkv_w"], qkv, self.qkv_w, Hd, lay["qkv_b"],
+                     self._epi_bias)
+            if prefill:
+                self._kv(li, lay, qkv, rows)
+                ops.attention(0, qkv, att, self.batch, rows, self.heads,
+                              self.hd, self._scale, stream=s, sync=False,
+                              causal=1, kv_heads=self._nkv)
+            else:
+                self._kv(li, lay, qkv, rows, att)
+            # h += proj; x = norm2(h); x2 = mlp(x)
+            if llama:
+                gemm(att, lay["proj_w"], x2, Hd, Hd)
+                norm(x2, lay["rms2_g"], None, x, res=h)
+                gemm(x, lay["gate_w"], ff, inter, Hd)
+                gemm(x, lay["up_w"], b["ff2"].data_ptr(), inter, Hd)
+                ops.silu_mul(0, ff, b["ff2"].data_ptr(), ff, M * inter,
+                             stream=s, sync=False)
+                gemm(ff, lay["down_w"], x2, Hd, inter)
+            else:
+                gemm(att, lay["proj_w"], x2, Hd, Hd, lay["proj_b"],
+                     self._epi_bias)
+                norm(x2, lay["ln2_g"], lay["ln2_b"], x, res=h)
+                gemm(x, lay["ff1_w"], ff, inter, Hd, lay["ff1_b"],
+                     self._epi_gelu)
+                gemm(ff, lay["ff2_w"], x2, Hd, inter, lay["ff2_b"],
+                     self._epi_bias)
+            # h += mlp; x = the next layer's norm1(h), or out = final norm
+            if li + 1 < self.n_layers:
+                norm(x2, *norm1(self.layers[li + 1]), x, res=h)
+            else:
+                norm(x2, self.lnf_g, self.lnf_b, out, res=h)
+
+    def _embed(self, ids, h, rows: int) -> None:
+        """h = tok[ids] + posemb[pos[b] + row] for `rows` rows per slot."""
+        self._C.ops.decode_embed(ids.data_ptr(), self.tok.data_ptr(),
+                                 self.posemb.data_ptr(), h.data_ptr(),
+                                 self.pos.data_ptr(), self.batch, rows,
+                                 self.smax, self.hidden, stream=self.stream,
+                                 sync=False)
+
+    def _head(self, x, logits, gids, M: int) -> None:
+        """Weight-tied lm head over M rows, then the greedy argmax ids."""
+        ops, s = self._C.ops, self.stream
+        ops.gemm_bt(0, x.data_ptr(), self.tok.data_ptr(), logits.data_ptr(),
+                    M=M, N=self.vocab, K=self.hidden, epi=self._epi_none,
+                    stream=s, sync=False)
+        ops.argmax_rows(logits.data_ptr(), gids.data_ptr(), M, self.vocab,
+                        stream=s, sync=False)
 
     def _enqueue(self):
         """Record one decode step's kernels on self.stream (pos-relative:
-        kv_append/decode_attention/embed all read the device counter).
-
-        The step is kernel-COUNT bound (~4.6 us graph-replay floor per
-        kernel regardless of size - profiles/dec_kernel_stats), so every
-        residual add is fused into the following layernorm (sum_out
-        updates the residual stream in the same kernel) and split-K is
-        disabled on the tiny M=B gemms via the tile hint (the fp32-slab
-        reduce kernel doubled the gemm count for no win at this floor).
-        """
-        if getattr(self, "arch", "gpt2") == "llama":
-            self._enqueue_llama()
-            return
-        if getattr(self, "fused", False):
+        embed / rope / kv_append / decode_attention all read the device
+        counter, which the last kernel advances)."""
+        if self.fused:
             self._enqueue_fused()
             return
-        C, s = self._C, self.stream
-        B, Hd = self.batch, self.hidden
-        T4 = 0  # heuristic tiles (split-K allowed)
-        ops = C.ops
-        ops.decode_embed(self.ids.data_ptr(), self.tok.data_ptr(),
-                         self.posemb.data_ptr(), self.h.data_ptr(),
-                         self.pos.data_ptr(), B, 1, self.smax, Hd, stream=s,
-                         sync=False)
-        ops.layernorm(0, self.h.data_ptr(),
-                      self.layers[0]["ln1_g"].data_ptr(),
-                      self.layers[0]["ln1_b"].data_ptr(), self.x.data_ptr(),
-                      B, Hd, stream=s, sync=False)
-        for li, lay in enumerate(self.layers):
-            ops.gemm_bt(0, self.x.data_ptr(), lay["qkv_w"].data_ptr(),
-                        self.qkv.data_ptr(), bias=lay["qkv_b"].data_ptr(),
-                        M=B, N=3 * Hd, K=Hd, epi=self._epi_bias, stream=s,
-                        sync=False, tile=T4)
-            self._kv(li, lay, self.qkv.data_ptr(), 1, self.att.data_ptr())
-            ops.gemm_bt(0, self.att.data_ptr(), lay["proj_w"].data_ptr(),
-                        self.x2.data_ptr(), bias=lay["proj_b"].data_ptr(),
-                        M=B, N=Hd, K=Hd, epi=self._epi_bias, stream=s,
-                        sync=False, tile=T4)
-            # h += proj; x = ln2(h)   (one kernel: sum_out = new residual)
-            ops.add_layernorm(0, self.x2.data_ptr(), self.h.data_ptr(),
-                              lay["ln2_g"].data_ptr(),
-                              lay["ln2_b"].data_ptr(), self.x.data_ptr(),
-                              sum_out=self.h.data_ptr(), M=B, N=Hd,
-                              stream=s, sync=False)
-            ops.gemm_bt(0, self.x.data_ptr(), lay["ff1_w"].data_ptr(),
-                        self.ff.data_ptr(), bias=lay["ff1_b"].data_ptr(),
-                        M=B, N=self.inter, K=Hd, epi=self._epi_gelu,
-                        stream=s, sync=False, tile=T4)
-            ops.gemm_bt(0, self.ff.data_ptr(), lay["ff2_w"].data_ptr(),
-                        self.x2.data_ptr(), bias=lay["ff2_b"].data_ptr(),
-                        M=B, N=Hd, K=self.inter, epi=self._epi_bias,
-                        stream=s, sync=False, tile=T4)
-            # h += ff2; x = next ln1(h) (or ln_f at the end)
-            nxt = (self.layers[li + 1] if li + 1 < self.n_layers else None)
-            gptr = (nxt["ln1_g"] if nxt else self.lnf_g).data_ptr()
-            bptr = (nxt["ln1_b"] if nxt else self.lnf_b).data_ptr()
-            dst = (self.x if nxt else self.out).data_ptr()
-            ops.add_layernorm(0, self.x2.data_ptr(), self.h.data_ptr(),
-                              gptr, bptr, dst, sum_out=self.h.data_ptr(),
-                              M=B, N=Hd, stream=s, sync=False)
+        self._embed(self.ids, self.h, 1)
+        self._forward(dict(h=self.h, x=self.x, qkv=self.qkv, att=self.att,
+                           x2=self.x2, ff=self.ff, ff2=self.ff2,
+                           out=self.out), "step", 1)
         if self.logits is not None:
-            ops.gemm_bt(0, self.out.data_ptr(), self.tok.data_ptr(),
-                        self.logits.data_ptr(), M=B, N=self.vocab, K=Hd,
-                        epi=self._epi_none, stream=s, sync=False)
-            ops.argmax_rows(self.logits.data_ptr(), self.gids.data_ptr(),
-                            B, self.vocab, stream=s, sync=False)
-        ops.advance_pos(self.pos.data_ptr(), B, self.smax, stream=s,
-                        sync=False)
+            self._head(self.out, self.logits, self.gids, self.batch)
+        self._C.ops.advance_pos(self.pos.data_ptr(), self.batch, self.smax,
+                                stream=self.stream, sync=False)
 
     def prefill(self, prompt: np.ndarray) -> np.ndarray:
         """Fill the KV caches from a whole prompt [B, P] in ONE pass through
@@ -636,103 +651,25 @@ class DecodeSession:
                 for li in range((Pp - 1) // 64 + 1):
                     self.kv_pool.ensure(b, li)
         M = B * Pp
-        Hd, inter = self.hidden, self.inter
+        Hd = self.hidden
         ops, s = self._C.ops, self.stream
 
+        def act(width):
+            return torch.empty(M, width, dtype=torch.half, device="cuda")
+
         dids = torch.from_numpy(ids.reshape(-1)).cuda()
-        h = torch.empty(M, Hd, dtype=torch.half, device="cuda")
-        x = torch.empty(M, Hd, dtype=torch.half, device="cuda")
-        x2 = torch.empty(M, Hd, dtype=torch.half, device="cuda")
-        qkv = torch.empty(M, self.qkv_w, dtype=torch.half, device="cuda")
-        ff = torch.empty(M, inter, dtype=torch.half, device="cuda")
-        ff2 = (torch.empty(M, inter, dtype=torch.half, device="cuda")
-               if self.arch == "llama" else None)
+        # three M x Hd buffers: attention writes into x, which is dead
+        # once the qkv GEMM has read it
+        h, x, x2 = act(Hd), act(Hd), act(Hd)
+        bufs = dict(h=h, x=x, att=x, x2=x2, out=x, qkv=act(self.qkv_w),
+                    ff=act(self.inter),
+                    ff2=act(self.inter) if self.arch == "llama" else None)
         torch.cuda.synchronize()
 
-        scale = 1.0 / float(np.sqrt(float(self.hd)))
         ops.embedding(0, dids.data_ptr(), self.tok.data_ptr(),
                       self.posemb.data_ptr(), out=h.data_ptr(), M=M, S=Pp,
                       H=Hd, stream=s, sync=False)
-        if self.arch == "llama":
-            ops.rmsnorm(0, h.data_ptr(),
-                        self.layers[0]["rms1_g"].data_ptr(), x.data_ptr(),
-                        M, Hd, eps=self.rms_eps, stream=s, sync=False)
-            for li, lay in enumerate(self.layers):
-                ops.gemm_bt(0, x.data_ptr(), lay["qkv_w"].data_ptr(),
-                            qkv.data_ptr(), M=M, N=self.qkv_w, K=Hd,
-                            epi=self._epi_none, stream=s, sync=False)
-                # full-sequence rope: pos = row % Pp (exact for rows < P;
-                # padded tail is causal-masked / overwritten before read)
-                ops.rope(0, qkv.data_ptr(), M=M, S=Pp, H=self.heads,
-                         D=self.hd, theta=self.theta, stream=s, sync=False,
-                         kv_heads=self._nkv)
-                self._kv(li, lay, qkv.data_ptr(), Pp)
-                ops.attention(0, qkv.data_ptr(), x2.data_ptr(), B, Pp,
-                              self.heads, self.hd, scale, stream=s,
-                              sync=False, causal=1, kv_heads=self._nkv)
-                ops.gemm_bt(0, x2.data_ptr(), lay["proj_w"].data_ptr(),
-                            x.data_ptr(), M=M, N=Hd, K=Hd,
-                            epi=self._epi_none, stream=s, sync=False)
-                ops.add_rmsnorm(0, x.data_ptr(), h.data_ptr(),
-                                lay["rms2_g"].data_ptr(), x2.data_ptr(),
-                                sum_out=h.data_ptr(), M=M, N=Hd, eps=self.rms_eps, stream=s,
-                                sync=False)
-                ops.gemm_bt(0, x2.data_ptr(), lay["gate_w"].data_ptr(),
-                            ff.data_ptr(), M=M, N=inter, K=Hd,
-                            epi=self._epi_none, stream=s, sync=False)
-                ops.gemm_bt(0, x2.data_ptr(), lay["up_w"].data_ptr(),
-                            ff2.data_ptr(), M=M, N=inter, K=Hd,
-                            epi=self._epi_none, stream=s, sync=False)
-                ops.silu_mul(0, ff.data_ptr(), ff2.data_ptr(),
-                             ff.data_ptr(), M * inter, stream=s, sync=False)
-                ops.gemm_bt(0, ff.data_ptr(), lay["down_w"].data_ptr(),
-                            x2.data_ptr(), M=M, N=Hd, K=inter,
-                            epi=self._epi_none, stream=s, sync=False)
-                nxt = (self.layers[li + 1] if li + 1 < self.n_layers
-                       else None)
-                gptr = (nxt["rms1_g"] if nxt else self.lnf_g).data_ptr()
-                ops.add_rmsnorm(0, x2.data_ptr(), h.data_ptr(), gptr,
-                                x.data_ptr(), sum_out=h.data_ptr(), M=M,
-                                N=Hd, eps=self.rms_eps, stream=s, sync=False)
-        else:
-            ops.layernorm(0, h.data_ptr(),
-                          self.layers[0]["ln1_g"].data_ptr(),
-                          self.layers[0]["ln1_b"].data_ptr(), x.data_ptr(),
-                          M, Hd, stream=s, sync=False)
-            for li, lay in enumerate(self.layers):
-                ops.gemm_bt(0, x.data_ptr(), lay["qkv_w"].data_ptr(),
-                            qkv.data_ptr(), bias=lay["qkv_b"].data_ptr(),
-                            M=M, N=3 * Hd, K=Hd, epi=self._epi_bias,
-                            stream=s, sync=False)
-                self._kv(li, lay, qkv.data_ptr(), Pp)
-                ops.attention(0, qkv.data_ptr(), x2.data_ptr(), B, Pp,
-                              self.heads, self.hd, scale,
-                              stream=s, sync=False, causal=1)
-                ops.gemm_bt(0, x2.data_ptr(), lay["proj_w"].data_ptr(),
-                            x.data_ptr(), bias=lay["proj_b"].data_ptr(),
-                            M=M, N=Hd, K=Hd, epi=self._epi_bias, stream=s,
-                            sync=False)
-                ops.add_layernorm(0, x.data_ptr(), h.data_ptr(),
-                                  lay["ln2_g"].data_ptr(),
-                                  lay["ln2_b"].data_ptr(), x2.data_ptr(),
-                                  sum_out=h.data_ptr(), M=M, N=Hd, stream=s,
-                                  sync=False)
-                ops.gemm_bt(0, x2.data_ptr(), lay["ff1_w"].data_ptr(),
-                            ff.data_ptr(), bias=lay["ff1_b"].data_ptr(),
-                            M=M, N=inter, K=Hd, epi=self._epi_gelu,
-                            stream=s, sync=False)
-                ops.gemm_bt(0, ff.data_ptr(), lay["ff2_w"].data_ptr(),
-                            x2.data_ptr(), bias=lay["ff2_b"].data_ptr(),
-                            M=M, N=Hd, K=inter, epi=self._epi_bias,
-                            stream=s, sync=False)
-                nxt = (self.layers[li + 1] if li + 1 < self.n_layers
-                       else None)
-                gptr = (nxt["ln1_g"] if nxt else self.lnf_g).data_ptr()
-                bptr = (nxt["ln1_b"] if nxt else self.lnf_b).data_ptr()
-                ops.add_layernorm(0, x2.data_ptr(), h.data_ptr(), gptr,
-                                  bptr, x.data_ptr(),
-                                  sum_out=h.data_ptr(), M=M, N=Hd,
-                                  stream=s, sync=False)
+        self._forward(bufs, "prefill", Pp)
         self._C.hip.stream_synchronize(s)
         # x holds ln_f(h) for every position; hand back the last real one
         last = x.reshape(B, Pp, Hd)[:, P - 1].contiguous()
@@ -773,139 +710,33 @@ class DecodeSession:
         arr = np.ascontiguousarray(ids, np.int32)
         # synchronous H2D keeps the token copy ordered before the replay
         self._C.memory.memcpy_h2d(self.ids.data_ptr(), arr, arr.nbytes)
-        if self.capture:
-            if not self._graph:
-                # step 0 runs eagerly as the warm-up, then a fresh step is
-                # RECORDED (capture does not execute) for replay from step 1
-                self._enqueue()
-                self._C.hip.stream_synchronize(self.stream)
-                self._C.hip.stream_begin_capture(self.stream)
-                self._enqueue()
-                self._graph = self._C.hip.stream_end_capture(self.stream)
-                self._steps += 1
-                self._slot_steps += 1
-                if return_ids:
-                    return self.gids.cpu().numpy()
-                out = self.out.float().cpu().numpy()
-                return (self.logits.float().cpu().numpy()
-                        if self.logits is not None else out)
+        if self._graph:
             self._C.hip.graph_launch(self._graph, self.stream)
         else:
             self._enqueue()
         self._C.hip.stream_synchronize(self.stream)
+        if self.capture and not self._graph:
+            # step 0 ran eagerly as the warm-up; now a fresh step is
+            # RECORDED (capture does not execute) for replay from step 1
+            self._C.hip.stream_begin_capture(self.stream)
+            self._enqueue()
+            self._graph = self._C.hip.stream_end_capture(self.stream)
         self._steps += 1
         self._slot_steps += 1
         if return_ids:
             return self.gids.cpu().numpy()
-        out = self.out.float().cpu().numpy()
-        return (self.logits.float().cpu().numpy()
-                if self.logits is not None else out)
+        if self.logits is not None:
+            return self.logits.float().cpu().numpy()
+        return self.out.float().cpu().numpy()
 
     # ------------------------------------------- speculative verification
     def _enqueue_chunk(self, cb: Dict, B: int, K: int) -> None:
         """Record one chunked-verification pass's kernels on the session
         stream (no syncs — capturable). All position dependence reads the
         device counter, so a captured chunk graph replays at any pos."""
-        M = B * K
-        Hd, inter = self.hidden, self.inter
-        ops, s = self._C.ops, self.stream
-        ops.decode_embed(cb["ids"].data_ptr(), self.tok.data_ptr(),
-                         self.posemb.data_ptr(), cb["h"].data_ptr(),
-                         self.pos.data_ptr(), B, K, self.smax, Hd, stream=s,
-                         sync=False)
-        if self.arch == "llama":
-            ops.rmsnorm(0, cb["h"].data_ptr(),
-                        self.layers[0]["rms1_g"].data_ptr(),
-                        cb["x"].data_ptr(), M, Hd, eps=self.rms_eps, stream=s, sync=False)
-            for li, lay in enumerate(self.layers):
-                ops.gemm_bt(0, cb["x"].data_ptr(), lay["qkv_w"].data_ptr(),
-                            cb["qkv"].data_ptr(), M=M, N=self.qkv_w, K=Hd,
-                            epi=self._epi_none, stream=s, sync=False)
-                # chunk rope: row b*K+i rotates at pos[b] + i
-                ops.rope(0, cb["qkv"].data_ptr(), pos=self.pos.data_ptr(),
-                         M=M, S=self.smax, H=self.heads, D=self.hd,
-                         theta=self.theta, stream=s, sync=False, chunk=K,
-                         kv_heads=self._nkv)
-                self._kv(li, lay, cb["qkv"].data_ptr(), K,
-                         cb["att"].data_ptr())
-                ops.gemm_bt(0, cb["att"].data_ptr(),
-                            lay["proj_w"].data_ptr(), cb["x2"].data_ptr(),
-                            M=M, N=Hd, K=Hd, epi=self._epi_none, stream=s,
-                            sync=False)
-                ops.add_rmsnorm(0, cb["x2"].data_ptr(), cb["h"].data_ptr(),
-                                lay["rms2_g"].data_ptr(),
-                                cb["x"].data_ptr(),
-                                sum_out=cb["h"].data_ptr(), M=M, N=Hd,
-                                eps=self.rms_eps, stream=s, sync=False)
-                ops.gemm_bt(0, cb["x"].data_ptr(), lay["gate_w"].data_ptr(),
-                            cb["ff"].data_ptr(), M=M, N=inter, K=Hd,
-                            epi=self._epi_none, stream=s, sync=False)
-                ops.gemm_bt(0, cb["x"].data_ptr(), lay["up_w"].data_ptr(),
-                            cb["ff2"].data_ptr(), M=M, N=inter, K=Hd,
-                            epi=self._epi_none, stream=s, sync=False)
-                ops.silu_mul(0, cb["ff"].data_ptr(), cb["ff2"].data_ptr(),
-                             cb["ff"].data_ptr(), M * inter, stream=s,
-                             sync=False)
-                ops.gemm_bt(0, cb["ff"].data_ptr(),
-                            lay["down_w"].data_ptr(), cb["x2"].data_ptr(),
-                            M=M, N=Hd, K=inter, epi=self._epi_none,
-                            stream=s, sync=False)
-                nxt = (self.layers[li + 1] if li + 1 < self.n_layers
-                       else None)
-                gptr = (nxt["rms1_g"] if nxt else self.lnf_g).data_ptr()
-                ops.add_rmsnorm(0, cb["x2"].data_ptr(), cb["h"].data_ptr(),
-                                gptr, cb["x"].data_ptr(),
-                                sum_out=cb["h"].data_ptr(), M=M, N=Hd,
-                                eps=self.rms_eps, stream=s, sync=False)
-        else:
-            ops.layernorm(0, cb["h"].data_ptr(),
-                          self.layers[0]["ln1_g"].data_ptr(),
-                          self.layers[0]["ln1_b"].data_ptr(),
-                          cb["x"].data_ptr(), M, Hd, stream=s, sync=False)
-            for li, lay in enumerate(self.layers):
-                ops.gemm_bt(0, cb["x"].data_ptr(), lay["qkv_w"].data_ptr(),
-                            cb["qkv"].data_ptr(),
-                            bias=lay["qkv_b"].data_ptr(),
-                            M=M, N=3 * Hd, K=Hd, epi=self._epi_bias,
-                            stream=s, sync=False)
-                self._kv(li, lay, cb["qkv"].data_ptr(), K,
-                         cb["att"].data_ptr())
-                ops.gemm_bt(0, cb["att"].data_ptr(),
-                            lay["proj_w"].data_ptr(), cb["x2"].data_ptr(),
-                            bias=lay["proj_b"].data_ptr(),
-                            M=M, N=Hd, K=Hd, epi=self._epi_bias, stream=s,
-                            sync=False)
-                ops.add_layernorm(0, cb["x2"].data_ptr(),
-                                  cb["h"].data_ptr(),
-                                  lay["ln2_g"].data_ptr(),
-                                  lay["ln2_b"].data_ptr(),
-                                  cb["x"].data_ptr(),
-                                  sum_out=cb["h"].data_ptr(), M=M, N=Hd,
-                                  stream=s, sync=False)
-                ops.gemm_bt(0, cb["x"].data_ptr(), lay["ff1_w"].data_ptr(),
-                            cb["ff"].data_ptr(),
-                            bias=lay["ff1_b"].data_ptr(),
-                            M=M, N=inter, K=Hd, epi=self._epi_gelu,
-                            stream=s, sync=False)
-                ops.gemm_bt(0, cb["ff"].data_ptr(), lay["ff2_w"].data_ptr(),
-                            cb["x2"].data_ptr(),
-                            bias=lay["ff2_b"].data_ptr(),
-                            M=M, N=Hd, K=inter, epi=self._epi_bias,
-                            stream=s, sync=False)
-                nxt = (self.layers[li + 1] if li + 1 < self.n_layers
-                       else None)
-                gptr = (nxt["ln1_g"] if nxt else self.lnf_g).data_ptr()
-                bptr = (nxt["ln1_b"] if nxt else self.lnf_b).data_ptr()
-                ops.add_layernorm(0, cb["x2"].data_ptr(),
-                                  cb["h"].data_ptr(),
-                                  gptr, bptr, cb["x"].data_ptr(),
-                                  sum_out=cb["h"].data_ptr(), M=M, N=Hd,
-                                  stream=s, sync=False)
-        ops.gemm_bt(0, cb["x"].data_ptr(), self.tok.data_ptr(),
-                    cb["logits"].data_ptr(), M=M, N=self.vocab, K=Hd,
-                    epi=self._epi_none, stream=s, sync=False)
-        ops.argmax_rows(cb["logits"].data_ptr(), cb["gids"].data_ptr(),
-                        M, self.vocab, stream=s, sync=False)
+        self._embed(cb["ids"], cb["h"], K)
+        self._forward(dict(cb, out=cb["x"]), "chunk", K)
+        self._head(cb["x"], cb["logits"], cb["gids"], B * K)
 
     def verify_chunk(self, tokens: np.ndarray,
                      greedy: bool = False) -> np.ndarray:
@@ -938,13 +769,9 @@ class DecodeSession:
         Hd, inter = self.hidden, self.inter
         s = self.stream
 
-        cbs = getattr(self, "_chunk_bufs_by_k", None)
-        if cbs is None:
-            cbs = self._chunk_bufs_by_k = {}
-            self._chunk_graphs = {}
-        cb = cbs.get(K)
+        cb = self._chunk_bufs_by_k.get(K)
         if cb is None:
-            cb = cbs[K] = dict(
+            cb = self._chunk_bufs_by_k[K] = dict(
                 K=K,
                 ids=torch.zeros(M, dtype=torch.int32, device="cuda"),
                 h=torch.zeros(M, Hd, dtype=torch.half, device="cuda"),
@@ -1001,7 +828,7 @@ class DecodeSession:
         if self.logits is None:
             raise RuntimeError("sample_tokens requires lm_head=True")
         torch = self._torch
-        if getattr(self, "_temps_dev", None) is None:
+        if self._temps_dev is None:
             self._temps_dev = torch.zeros(self.batch, dtype=torch.float32,
                                           device="cuda")
             self._seeds_dev = torch.zeros(self.batch, dtype=torch.int32,
@@ -1019,7 +846,7 @@ class DecodeSession:
                 seeds=self._seeds_dev.data_ptr(), pos=self.pos.data_ptr(),
                 M=self.batch, V=self.vocab, stream=self.stream, sync=True)
             return self.gids.cpu().numpy()
-        if getattr(self, "_topk_dev", None) is None:
+        if self._topk_dev is None:
             self._topk_dev = torch.zeros(self.batch, dtype=torch.int32,
                                          device="cuda")
             self._topp_dev = torch.zeros(self.batch, dtype=torch.float32,
@@ -1098,10 +925,9 @@ class DecodeSession:
         if self._graph:
             self._C.hip.graph_destroy(self._graph)
             self._graph = 0
-        for g in getattr(self, "_chunk_graphs", {}).values():
+        for g in self._chunk_graphs.values():
             self._C.hip.graph_destroy(g)
-        if getattr(self, "_chunk_graphs", None):
-            self._chunk_graphs = {}
+        self._chunk_graphs = {}
 
     def __del__(self):
         try:
